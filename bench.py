@@ -9,11 +9,23 @@ per GPU) every rank owns its own 1M-observer shard (observers are
 range-partitioned; scoring needs no exchange), so scaling is weak and `value`
 is the records all ranks refreshed / the slowest rank's time.
 
-Rank 0 at N=1 also times the CPU oracle (oracle/, a single-threaded C
-restatement of score.go) on the same state for `cpu_baseline`, and checks
-that the GPU scores of that pass are bit-identical to it.
+A plain run does only what the headline needs: it builds the overlay and the
+engine, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step` and the headline kernel's roofline from the HIP events of the
+timed steps themselves).  --dump-outputs DIR also writes what the last timed
+step computed, the scores a caller of gsx_scores() receives, as DIR/scores.npy
+(float64; a fixed seeded sample of the pairs when they exceed DUMP_MAX_SCORES).
+The inputs are seeded, so two runs with the same arguments dump the same array.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+--full adds every other leg to the line: the one-observer view, message
+propagation (replica, its variants, the cfg4 overlay), the heartbeat rounds,
+the cfg5 adversarial overlay, the drop-in scorer latency, and at N=1 on rank 0
+the CPU oracle (oracle/, a C restatement of score.go) timed on the same state
+for `cpu_baseline`, with a check that the GPU scores of that pass are
+bit-identical to it.  The leg options below (--prop-*, --hb-*, --adv-peers,
+--no-cpu, ...) shape those legs and have no effect without --full.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -39,6 +51,8 @@ HBM_COPY_GBS = 6290.0  # measured float4 copy on MI355X (MI355X_MICROARCH.md): t
 BYTES_PER_RECORD = 82  # read fmd,mmd,mfp,imd,graftTime,flags; write the same with meshTime
 BYTES_PER_PAIR = 49  # read bp, app, p6, expire, connected; write bp, score
 T0 = 1_700_000_000 * abi.SECOND
+DUMP_MAX_SCORES = 6_000_000  # --dump-outputs: at most 48 MB of float64 scores
+DUMP_SEED = 0x5C0FE5  # of the sample's pair indices (fixed: two builds dump the same pairs)
 
 
 def log(*a):
@@ -64,6 +78,25 @@ def build_engine(n, T, d, seed, device):
     e.set_app_scores(np.zeros(ov.n_pairs))
     log(f"[bench] engine loaded + state synthesized in {time.time() - t:.1f}s")
     return ov, e
+
+
+def dump_sample(n_pairs):
+    """The pairs --dump-outputs keeps: all of them up to DUMP_MAX_SCORES, else a
+    sorted sample of that many drawn with DUMP_SEED (the same for every run)."""
+    if n_pairs <= DUMP_MAX_SCORES:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_pairs, size=DUMP_MAX_SCORES, replace=False))
+
+
+def dump_outputs(path, e):
+    """DIR/scores.npy: what the last timed gsx_refresh() left for gsx_scores(),
+    float64 per pair in pair order (dump_sample's pairs of a larger shard)."""
+    sc = e.scores()
+    idx = dump_sample(len(sc))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "scores.npy"), sc if idx is None else sc[idx])
+    log(f"[bench] scores of the last step written to {os.path.join(path, 'scores.npy')} "
+        f"({len(sc) if idx is None else len(idx)} of {len(sc)} pairs)")
 
 
 PMC_FILE = "pmc_r06.json"  # written by tools/pmc.sh (tools/pmc_bytes.py)
@@ -736,6 +769,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step to DIR/scores.npy (float64, rank 0's shard)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (single observer, propagation, heartbeat, adversarial, "
+                         "drop-in latency, CPU baselines and the parity check against the oracle)")
     ap.add_argument("--peers", type=int, default=1_000_000)
     ap.add_argument("--topics", type=int, default=8)
     ap.add_argument("--degree", type=int, default=6)
@@ -767,8 +805,14 @@ def main():
     ap.add_argument("--rehearse", action="store_true",
                     help="N>1 rehearsal on one GPU: all ranks on device 0, gloo (host-staged) instead of RCCL")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline alone
+        args.single_observer = args.dropin = False
+        args.no_cpu = True
+        args.prop_msgs = args.prop_peers = args.hb_steps = args.adv_peers = 0
 
-    rank = int(os.environ.get("RANK", "0"))
+    rank =int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if args.rehearse:  # every rank on GPU 0, gloo through host memory: the multi-GPU flow on one card
@@ -818,6 +862,8 @@ def main():
     barrier()
     elapsed = t1 - t0
     k_total, k_min, k_max, k_n = e.timing_end()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, e)
 
     recs = float(R) * args.steps
     elapsed = reduce_scalar(elapsed, dist, dev, "max")
@@ -988,6 +1034,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,  # False: the secondary legs below did not run (null)
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",

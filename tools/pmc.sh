@@ -33,7 +33,7 @@ for C in FETCH_SIZE WRITE_SIZE; do
         --prop-peers 0 --hb-steps 0 --adv-peers 0
     want p1024 && run p1024 200 $C python3 tools/prop_profile.py --msgs 1024 --batches 3 --warmup 2
     want p64 && run p64 200 $C python3 tools/prop_profile.py --msgs 64 --batches 3 --warmup 2
-    want hb && run hb 300 $C python3 bench.py --steps 1 --warmup 0 --no-cpu --no-dropin --no-single-observer --prop-msgs 0 \
+    want hb && run hb 300 $C python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-dropin --no-single-observer --prop-msgs 0 \
         --prop-peers 0 --adv-peers 0 --hb-steps 5
 done
 python3 tools/pmc_bytes.py "$O" "n=1000000,T=8,d=6,E=11999954" ${PMC_MERGE:-} > "$O/summary.json" && cat "$O/summary.json"
