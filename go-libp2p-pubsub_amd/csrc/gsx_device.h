@@ -66,9 +66,29 @@ __host__ __device__ __forceinline__ size_t flag_index(uint64_t p, uint32_t t, ui
     return ((p / TILE) * n_topics + t) * TILE + (p % TILE);
 }
 
+// Zero map of the two penalty counters (most peers never send an invalid
+// message, most meshes never fail):
+//   zmap  [p/64][t][2]          u8 per (tile, topic, field = MFP, IMD)
+// ZM_ZERO: the stored field is bitwise +0.0 for every present pair of the tile
+// and topic, so the refresh pass does not load it.  ZM_MAYBE says nothing.
+// rec stays the only source of truth: every store of a value that may be
+// non-zero marks the byte first (zmap_mark, gsx_ops.h: a plain byte store of
+// the constant, never a read-modify-write), and only the refresh pass clears
+// one, when all 64 pairs of the tile are present and hold +0.0 after the
+// decay.  A wave's entries for all its topics are contiguous (16 B at T = 8).
+constexpr uint8_t ZM_ZERO = 0, ZM_MAYBE = 1;
+__host__ __device__ __forceinline__ size_t zmap_index(uint64_t p, uint32_t t, uint32_t n_topics, int field) {
+    return ((p / TILE) * n_topics + t) * 2 + (size_t)(field - MFP);  // field: MFP or IMD
+}
+// bytes of the map: whole 32-bit words (the refresh pass reads it as such)
+__host__ __device__ __forceinline__ size_t zmap_bytes(uint64_t n_tiles, uint32_t n_topics) {
+    return ((n_tiles * n_topics * 2 + 3) / 4 + 1) * 4;
+}
+
 struct DevState {
     double* rec;          // tiled records (GRAFT slot holds int64 bits)
     uint8_t* rflags;      // tiled record flags
+    uint8_t* zmap;        // per (tile, topic, MFP | IMD): ZM_ZERO / ZM_MAYBE
     uint8_t* pflags;      // per pair: PRESENT | CONNECTED
     int64_t* expire;      // per pair: retention expiry
     double* bp;           // per pair: behaviourPenalty
@@ -912,4 +932,9 @@ hipError_t launch_mesh_time_export(const DevState& s, int64_t* topic_major, hipS
 // Sets FRESH on in-mesh records whose imported meshTime is 0; counts records
 // whose meshTime is neither 0 nor last_refresh - graftTime into *n_bad.
 hipError_t launch_mesh_time_import(const DevState& s, const int64_t* topic_major, uint32_t* n_bad, hipStream_t st);
+// Counts into *n_bad the zero-map entries that say ZM_ZERO while a present
+// pair of their tile holds another bit pattern than +0.0 (always 0: a check).
+hipError_t launch_zmap_check(const DevState& s, uint32_t* n_bad, hipStream_t st);
+// Counts into *n_marked the zero-map entries that say ZM_MAYBE.
+hipError_t launch_zmap_marked(const DevState& s, uint32_t* n_marked, hipStream_t st);
 }  // namespace gsx

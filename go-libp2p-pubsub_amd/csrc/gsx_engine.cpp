@@ -91,6 +91,7 @@ struct gsx_engine {
     // device state
     double* d_rec = nullptr;      // tiled records, gsx_device.h
     uint8_t* d_rflags = nullptr;  // tiled record flags
+    uint8_t* d_zmap = nullptr;    // zero map of MFP / IMD per (tile, topic), gsx_device.h
     void* d_tmp = nullptr;        // import/export staging of one topic-major field
     uint32_t* d_nbad = nullptr;
     uint8_t *d_pflags = nullptr, *d_eflags = nullptr;
@@ -573,6 +574,7 @@ gsx::DevState dev_state(const gsx_engine* e) {
     gsx::DevState s{};
     s.rec = e->d_rec;
     s.rflags = e->d_rflags;
+    s.zmap = e->d_zmap;
     s.pflags = e->d_pflags;
     s.expire = e->d_expire;
     s.bp = e->d_bp;
@@ -850,10 +852,11 @@ void free_state(gsx_engine* e) {
     gx_abort(e);
     void* ptrs[] = {e->d_rec,    e->d_rflags, e->d_tmp, e->d_nbad,    e->d_pflags, e->d_eflags,
                     e->d_expire, e->d_bp,     e->d_app, e->d_score,   e->d_ipg,    e->d_ipcount,
-                    e->d_col};
+                    e->d_col,    e->d_zmap};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     e->d_rec = nullptr;
+    e->d_zmap = nullptr;
     e->d_tmp = nullptr;
     e->d_nbad = nullptr;
     e->d_rflags = e->d_pflags = e->d_eflags = nullptr;
@@ -1639,6 +1642,7 @@ int load_overlay(gsx_engine* e, uint32_t n_total, uint32_t node_lo, uint32_t n_n
     const size_t R = (size_t)e->T * e->n_tiles * gsx::TILE;  // record slots, tail of the last tile unused
     int rc = 0;
     if ((rc = dalloc(e, &e->d_rec, R * gsx::NFIELD)) || (rc = dalloc(e, &e->d_rflags, R)) ||
+        (rc = dalloc(e, &e->d_zmap, gsx::zmap_bytes(e->n_tiles, e->T))) ||
         (rc = dalloc(e, &e->d_nbad, 1)) || (rc = dalloc(e, &e->d_pflags, e->rs)) ||
         (rc = dalloc(e, &e->d_eflags, e->rs)) || (rc = dalloc(e, &e->d_expire, e->rs)) ||
         (rc = dalloc(e, &e->d_bp, e->rs)) || (rc = dalloc(e, &e->d_app, e->rs)) ||
@@ -1651,6 +1655,8 @@ int load_overlay(gsx_engine* e, uint32_t n_total, uint32_t node_lo, uint32_t n_n
     }
     HIPCHK(e, hipMemsetAsync(e->d_rec, 0, sizeof(double) * R * gsx::NFIELD, e->stream));
     HIPCHK(e, hipMemsetAsync(e->d_rflags, 0, R, e->stream));
+    // every record is +0.0: the zero map says so everywhere (ZM_ZERO == 0)
+    HIPCHK(e, hipMemsetAsync(e->d_zmap, gsx::ZM_ZERO, gsx::zmap_bytes(e->n_tiles, e->T), e->stream));
     HIPCHK(e, hipMemsetAsync(e->d_pflags, 0, e->rs, e->stream));
     HIPCHK(e, hipMemsetAsync(e->d_expire, 0, sizeof(int64_t) * e->rs, e->stream));
     HIPCHK(e, hipMemsetAsync(e->d_bp, 0, sizeof(double) * e->rs, e->stream));
@@ -2466,6 +2472,30 @@ int gsx_export_state(gsx_engine* e, gsx_state_view* s) {
     s->last_refresh_ns = e->last_refresh;
     return GSX_OK;
 }
+
+// One of the zero map's counts: the entries that break its invariant, or
+// (marked) the entries that say "maybe non-zero".
+static int zero_map_count(gsx_engine* e, uint64_t* n, bool marked) {
+    if (!e || !n) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    if (int rc = fold_deferred(e)) return rc;
+    if (int rc = flush(e)) return rc;
+    uint32_t n_bad = 0;
+    HIPCHK(e, hipMemsetAsync(e->d_nbad, 0, sizeof(uint32_t), e->stream));
+    if (marked) {
+        HIPCHK(e, gsx::launch_zmap_marked(dev_state(e), e->d_nbad, e->stream));
+    } else {
+        HIPCHK(e, gsx::launch_zmap_check(dev_state(e), e->d_nbad, e->stream));
+    }
+    HIPCHK(e, hipMemcpyAsync(&n_bad, e->d_nbad, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    *n = n_bad;
+    return GSX_OK;
+}
+
+int gsx_zero_map_violations(gsx_engine* e, uint64_t* n) { return zero_map_count(e, n, false); }
+int gsx_zero_map_marked(gsx_engine* e, uint64_t* n) { return zero_map_count(e, n, true); }
 
 // inspectScoresExtended, score.go:463-493
 int gsx_peer_score_snapshot(gsx_engine* e, gsx_score_snapshot* s) {

@@ -419,6 +419,7 @@ __device__ __forceinline__ void apply_events(const DevState& s, const HbState& h
                 const double mmd = s.rec[b + MMD * TILE];
                 if (mmd < threshold) {
                     const double deficit = threshold - mmd;
+                    zmap_mark(s, r, t, MFP);
                     s.rec[b + MFP * TILE] = s.rec[b + MFP * TILE] + deficit * deficit;
                 }
             }

@@ -17,6 +17,22 @@ namespace gsx {
 
 // ---- hot path: fused refresh + score ---------------------------------------
 
+// x is the same in every lane of the wave: says so to the compiler, which then
+// keeps it (and what is loaded through it) in scalar registers.
+__device__ __forceinline__ uint64_t wave_uniform(uint64_t x) {
+    return (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)x) |
+           (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(x >> 32)) << 32;
+}
+
+// The zero-map bytes of one (tile, topic) at the even byte offset o, MFP's in
+// bits 0-7 and IMD's in bits 8-15, read through their aligned 32-bit word (a
+// scalar load: the offset is wave-uniform).
+constexpr uint32_t ZM_MFP_BITS = 0x00FFu, ZM_IMD_BITS = 0xFF00u;
+__device__ __forceinline__ uint32_t zmap_pair(const uint8_t* zmap, uint64_t o) {
+    const uint32_t w = reinterpret_cast<const uint32_t*>(zmap)[o >> 2];
+    return __builtin_amdgcn_readfirstlane((w >> ((uint32_t)(o & 2) * 8)) & 0xFFFFu);
+}
+
 template <int TT, bool REFRESH>
 __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp, int64_t now,
                                                        const uint8_t* __restrict__ only,
@@ -31,6 +47,19 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
     // with only2 also marked there): the others keep their cached score, a
     // wave without one returns at once
     if (!REFRESH && only && (!only[p] || (only2 && !only2[p]))) return;
+    const int T = TT > 0 ? TT : (int)s.n_topics;
+    const uint64_t lane = p % TILE;
+    // The wave's zero-map entries (gsx_device.h), read once and before the
+    // record loads, beside the pair flags: a counter whose entry says zero is
+    // not loaded, its value is the constant +0.0 and the arithmetic below is
+    // unchanged (decay(0) = 0 is not written back, 0 * 0 * w4 adds the same
+    // zero).  The record loads wait on nothing else.
+    const uint64_t zoff = wave_uniform(p / TILE) * (uint64_t)T * 2;
+    uint32_t zm[TT > 0 ? TT : 1];
+    if constexpr (TT > 0) {
+#pragma unroll
+        for (int t = 0; t < TT; ++t) zm[t] = zmap_pair(s.zmap, zoff + 2 * t);
+    }
     const uint8_t st = s.pflags[p];
     if (!(st & PAIR_PRESENT)) {  // no peerStats: Score() returns 0 (:259-262)
         s.score[p] = 0.0;
@@ -39,15 +68,13 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
     const DevPeerParams& pp = kp.pp;
     // Disconnected (retained) peers are not decayed (:503-516).
     const bool conn = REFRESH && (st & PAIR_CONNECTED);
-    const int T = TT > 0 ? TT : (int)s.n_topics;
-    const uint64_t lane = p % TILE;
     double* const tile = s.rec + (p / TILE) * (uint64_t)T * (NFIELD * TILE) + lane;
     uint8_t* const ftile = s.rflags + (p / TILE) * (uint64_t)T * TILE + lane;
     double score = 0.0;
     // One topic's refresh (decay, write-back of changed counters, meshTime /
     // activation) and score term, from its already-loaded record.
     auto topic_step = [&](int t, const DevTopicParams& tp, double fmd, double mmd, double mfp, double imd,
-                          int64_t graft, uint8_t fl) {
+                          int64_t graft, uint8_t fl, uint32_t zmt) {
         double* const r = tile + (uint64_t)t * (NFIELD * TILE);
         int64_t mt = 0;
         if (conn) {
@@ -74,6 +101,17 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
         } else if ((fl & REC_IN_MESH) && !(fl & REC_FRESH)) {
             mt = s.last_refresh - graft;
         }
+        if constexpr (REFRESH) {
+            // a marked counter that is +0.0 again in all 64 pairs of the tile
+            // (all present: no lane returned above): one lane clears the mark
+            if (zmt && __ballot(1) == ~0ull) {
+                uint8_t* const zb = s.zmap + zoff + 2 * t;
+                const bool z3 = (zmt & ZM_MFP_BITS) && __ballot(__double_as_longlong(mfp) != 0) == 0;
+                const bool z4 = (zmt & ZM_IMD_BITS) && __ballot(__double_as_longlong(imd) != 0) == 0;
+                if (z3 && lane == 0) zb[0] = ZM_ZERO;
+                if (z4 && lane == 0) zb[1] = ZM_ZERO;
+            }
+        }
         score += topic_score(tp, fl, mt, fmd, mmd, mfp, imd);
     };
     // streamed once per pass: non-temporal loads/stores (measured +4 %, tools/microbench)
@@ -92,8 +130,8 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
             const double* const r = tile + (uint64_t)t * (NFIELD * TILE);
             fmd[t] = __builtin_nontemporal_load(r + FMD * TILE);
             mmd[t] = __builtin_nontemporal_load(r + MMD * TILE);
-            mfp[t] = __builtin_nontemporal_load(r + MFP * TILE);
-            imd[t] = __builtin_nontemporal_load(r + IMD * TILE);
+            mfp[t] = (zm[t] & ZM_MFP_BITS) ? __builtin_nontemporal_load(r + MFP * TILE) : 0.0;
+            imd[t] = (zm[t] & ZM_IMD_BITS) ? __builtin_nontemporal_load(r + IMD * TILE) : 0.0;
             fl[t] = ftile[t * TILE];
             // with one topic there is nothing to overlap the flag load with,
             // and skipping graftTime outside the mesh saves its line (cfg5)
@@ -104,17 +142,20 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
 #pragma unroll
         for (int t = 0; t < TT; ++t) {
             if (!kp.tp[t].scored) continue;
-            topic_step(t, kp.tp[t], fmd[t], mmd[t], mfp[t], imd[t], gr[t], fl[t]);
+            topic_step(t, kp.tp[t], fmd[t], mmd[t], mfp[t], imd[t], gr[t], fl[t], zm[t]);
         }
     } else {
         for (int t = 0; t < T; ++t) {
             const DevTopicParams& tp = s.tp[t];
             if (!tp.scored) continue;
             const double* const r = tile + (uint64_t)t * (NFIELD * TILE);
+            const uint32_t zmt = zmap_pair(s.zmap, zoff + 2 * t);
             const uint8_t fl = ftile[t * TILE];
             const int64_t graft = (fl & REC_IN_MESH) ? reinterpret_cast<const int64_t*>(r)[GRAFT * TILE] : 0;
-            topic_step(t, tp, __builtin_nontemporal_load(r + FMD * TILE), __builtin_nontemporal_load(r + MMD * TILE),
-                       __builtin_nontemporal_load(r + MFP * TILE), __builtin_nontemporal_load(r + IMD * TILE), graft, fl);
+            const double fmd = __builtin_nontemporal_load(r + FMD * TILE), mmd = __builtin_nontemporal_load(r + MMD * TILE);
+            const double mfp = (zmt & ZM_MFP_BITS) ? __builtin_nontemporal_load(r + MFP * TILE) : 0.0;
+            const double imd = (zmt & ZM_IMD_BITS) ? __builtin_nontemporal_load(r + IMD * TILE) : 0.0;
+            topic_step(t, tp, fmd, mmd, mfp, imd, graft, fl, zmt);
         }
     }
     double bp = s.bp[p];
@@ -237,9 +278,11 @@ __global__ __launch_bounds__(256) void k_tile_field(DevState s, int field, const
     const uint32_t t = blockIdx.y;
     if (p >= s.n_pairs) return;
     const size_t i = (size_t)t * s.n_pairs + p;
-    if (field < NFIELD)
-        s.rec[rec_index(p, t, s.n_topics, field)] = static_cast<const double*>(src)[i];
-    else
+    if (field < NFIELD) {
+        const double v = static_cast<const double*>(src)[i];
+        if ((field == MFP || field == IMD) && __double_as_longlong(v) != 0) zmap_mark(s, p, t, field);
+        s.rec[rec_index(p, t, s.n_topics, field)] = v;
+    } else
         s.rflags[flag_index(p, t, s.n_topics)] = static_cast<const uint8_t*>(src)[i] & (REC_IN_MESH | REC_ACTIVE);
 }
 
@@ -278,6 +321,30 @@ __global__ __launch_bounds__(256) void k_mesh_time_import(DevState s, const int6
     else if (mt != s.last_refresh - graft) atomicAdd(n_bad, 1u);
 }
 
+// The zero map's invariant, checked: one wave per (tile, topic); an entry that
+// says zero while a present pair of the tile holds anything but +0.0 counts.
+__global__ __launch_bounds__(256) void k_zmap_check(DevState s, uint32_t* n_bad) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t t = blockIdx.y;
+    bool bad3 = false, bad4 = false;
+    if (p < s.n_pairs && (s.pflags[p] & PAIR_PRESENT)) {
+        const size_t b = rec_index(p, t, s.n_topics, FMD);
+        const unsigned long long* const r = reinterpret_cast<const unsigned long long*>(s.rec);
+        bad3 = s.zmap[zmap_index(p, t, s.n_topics, MFP)] == ZM_ZERO && r[b + MFP * TILE] != 0;
+        bad4 = s.zmap[zmap_index(p, t, s.n_topics, IMD)] == ZM_ZERO && r[b + IMD * TILE] != 0;
+    }
+    const uint32_t n = (__ballot(bad3) != 0) + (__ballot(bad4) != 0);
+    if (n && threadIdx.x % TILE == 0) atomicAdd(n_bad, n);
+}
+
+// Entries of the zero map that say "maybe non-zero" (one wave atomic each).
+__global__ __launch_bounds__(256) void k_zmap_marked(DevState s, uint32_t* n_marked) {
+    const uint64_t n = (s.n_pairs + TILE - 1) / TILE * s.n_topics * 2;
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t b = __ballot(i < n && s.zmap[i] != ZM_ZERO);
+    if (b && threadIdx.x % 64 == 0) atomicAdd(n_marked, (uint32_t)__popcll(b));
+}
+
 // ---- seeded synthetic state (gsx/synth.py restated on the device) ------------
 
 __device__ __forceinline__ double unif(uint64_t seed, uint64_t tag, uint64_t a, uint64_t b) {
@@ -294,9 +361,13 @@ __global__ __launch_bounds__(256) void k_synth_records(DevState s, const int32_t
     const size_t b = rec_index(p, t, s.n_topics, FMD);
     s.rec[b + FMD * TILE] = unif(sp.seed, TAG_STATE, a, 1) * sp.fmd_max;
     s.rec[b + MMD * TILE] = unif(sp.seed, TAG_STATE, a, 2) * sp.mmd_max;
-    s.rec[b + MFP * TILE] = unif(sp.seed, TAG_STATE, a, 3) * sp.mfp_max;
+    const double v3 = unif(sp.seed, TAG_STATE, a, 3) * sp.mfp_max;
     const double u4 = unif(sp.seed, TAG_STATE, a, 4) * sp.imd_max;
-    s.rec[b + IMD * TILE] = ((uint32_t)col[p] >= sp.sybil_first) ? u4 : 0.0;
+    const double v4 = ((uint32_t)col[p] >= sp.sybil_first) ? u4 : 0.0;
+    if (__double_as_longlong(v3) != 0) zmap_mark(s, p, t, MFP);
+    if (__double_as_longlong(v4) != 0) zmap_mark(s, p, t, IMD);
+    s.rec[b + MFP * TILE] = v3;
+    s.rec[b + IMD * TILE] = v4;
     const bool in_mesh = unif(sp.seed, TAG_STATE, a, 5) < sp.p_in_mesh;
     const int64_t graft = sp.now - (int64_t)(unif(sp.seed, TAG_STATE, a, 6) * (double)sp.graft_window);
     reinterpret_cast<int64_t*>(s.rec)[b + GRAFT * TILE] = graft;
@@ -464,6 +535,19 @@ hipError_t launch_untile_field(const DevState& s, int field, void* dst, hipStrea
 hipError_t launch_mesh_time_export(const DevState& s, int64_t* dst, hipStream_t st) {
     if (s.n_pairs == 0) return hipSuccess;
     hipLaunchKernelGGL(k_mesh_time_export, dim3(blocks_for(s.n_pairs, 256), s.n_topics), dim3(256), 0, st, s, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_zmap_check(const DevState& s, uint32_t* n_bad, hipStream_t st) {
+    if (s.n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_zmap_check, dim3(blocks_for(s.n_pairs, 256), s.n_topics), dim3(256), 0, st, s, n_bad);
+    return hipGetLastError();
+}
+
+hipError_t launch_zmap_marked(const DevState& s, uint32_t* n_marked, hipStream_t st) {
+    if (s.n_pairs == 0) return hipSuccess;
+    const uint64_t n = (s.n_pairs + TILE - 1) / TILE * s.n_topics * 2;
+    hipLaunchKernelGGL(k_zmap_marked, dim3(blocks_for(n, 256)), dim3(256), 0, st, s, n_marked);
     return hipGetLastError();
 }
 

@@ -146,6 +146,13 @@ __device__ __forceinline__ void ipcount_add(const DevState& s, uint64_t p, int d
     if (g.y != IPG_NONE && g.y != g.x) s.ipcount[g.y & ~IPG_WL] += (uint32_t)delta;
 }
 
+// Every store to a record's MFP / IMD of a value that may be non-zero goes with
+// this mark (the zero map's invariant, gsx_device.h).  A plain byte store of
+// the constant: lanes racing on one tile's byte all write the same value.
+__device__ __forceinline__ void zmap_mark(const DevState& s, uint64_t p, uint32_t t, int field) {
+    s.zmap[zmap_index(p, t, s.n_topics, field)] = ZM_MAYBE;
+}
+
 __device__ __forceinline__ bool scored_topic(const DevState& s, uint64_t p, uint32_t topic) {
     return (s.pflags[p] & PAIR_PRESENT) && topic < s.n_topics && s.tp[topic].scored;
 }
@@ -184,6 +191,7 @@ __device__ inline void ev_remove_peer(const DevState& s, const DevPeerParams& pp
         const double mmd = s.rec[b + MMD * TILE];
         if ((fl & REC_IN_MESH) && (fl & REC_ACTIVE) && mmd < threshold) {
             const double deficit = threshold - mmd;
+            zmap_mark(s, p, t, MFP);
             s.rec[b + MFP * TILE] = s.rec[b + MFP * TILE] + deficit * deficit;
         }
         s.rflags[fi] = fl & ~(REC_IN_MESH | REC_FRESH);
@@ -207,6 +215,7 @@ __device__ inline void ev_prune(const DevState& s, uint64_t p, uint32_t topic) {
     const double mmd = s.rec[b + MMD * TILE];
     if ((fl & REC_ACTIVE) && mmd < threshold) {
         const double deficit = threshold - mmd;
+        zmap_mark(s, p, topic, MFP);
         s.rec[b + MFP * TILE] = s.rec[b + MFP * TILE] + deficit * deficit;
     }
     s.rflags[fi] = fl & ~(REC_IN_MESH | REC_FRESH);
@@ -237,6 +246,7 @@ __device__ inline void ev_mesh(const DevState& s, uint64_t p, uint32_t topic) { 
 __device__ inline void ev_invalid(const DevState& s, uint64_t p, uint32_t topic) {  // :894-907
     if (!scored_topic(s, p, topic)) return;
     const size_t b = rec_index(p, topic, s.n_topics, IMD);
+    zmap_mark(s, p, topic, IMD);
     s.rec[b] = s.rec[b] + 1;
 }
 

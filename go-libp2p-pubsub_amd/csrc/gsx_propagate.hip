@@ -1771,7 +1771,10 @@ __device__ __forceinline__ void fold_pair(const PropState& ps, const DevState& s
     const DevTopicParams& tp = s.tp[ps.topic];
     const size_t b = rec_index(q, ps.topic, s.n_topics, FMD);
     // markInvalidMessageDelivery (score.go:894-907): k4 steps of +1, no cap
-    if (k4) s.rec[b + IMD * TILE] = add_ones_capped(s.rec[b + IMD * TILE], k4, __builtin_inf());
+    if (k4) {
+        zmap_mark(s, q, ps.topic, IMD);
+        s.rec[b + IMD * TILE] = add_ones_capped(s.rec[b + IMD * TILE], k4, __builtin_inf());
+    }
     if (k1 == 0 && k2 == 0) return;
     s.rec[b + FMD * TILE] = add_ones_capped(s.rec[b + FMD * TILE], k1, tp.cap2);
     if (!(s.rflags[flag_index(q, ps.topic, s.n_topics)] & REC_IN_MESH)) return;
@@ -1930,6 +1933,7 @@ __device__ __forceinline__ void fold_rescore_1(const PropState& ps, const DevSta
         const uint32_t k1 = fa[i], k2 = da[i], k4 = k4a[i];
         if (k4) {
             imd[j] = add_ones_capped(imd[j], k4, __builtin_inf());
+            zmap_mark(s, q, t, IMD);
             s.rec[b + IMD * TILE] = imd[j];
         }
         if (k1 | k2) {

@@ -417,6 +417,8 @@ SIGNATURES = {
     "gsx_settle_scores": (C.c_int, [C.c_void_p]),
     "gsx_import_state": (C.c_int, [C.c_void_p, P(StateView)]),
     "gsx_export_state": (C.c_int, [C.c_void_p, P(StateView)]),
+    "gsx_zero_map_violations": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
+    "gsx_zero_map_marked": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
     "gsx_last_refresh_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "gsx_synthesize_state": (C.c_int, [C.c_void_p, P(SynthSpec)]),
     "gsx_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, P(PropConfig), P(PropOut)]),

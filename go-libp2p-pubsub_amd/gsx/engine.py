@@ -760,3 +760,15 @@ class Engine:
         self._chk(self.lib.gsx_export_state(self.h, C.byref(sv)), "gsx_export_state")
         out["last_refresh_ns"] = int(sv.last_refresh_ns)
         return out
+
+    def zero_map_violations(self) -> int:
+        """gsx_zero_map_violations: zero-map entries that say zero over a non-zero counter (always 0)."""
+        n = C.c_uint64()
+        self._chk(self.lib.gsx_zero_map_violations(self.h, C.byref(n)), "gsx_zero_map_violations")
+        return n.value
+
+    def zero_map_marked(self) -> int:
+        """gsx_zero_map_marked: zero-map entries (tile, topic, counter) that say "maybe non-zero"."""
+        n = C.c_uint64()
+        self._chk(self.lib.gsx_zero_map_marked(self.h, C.byref(n)), "gsx_zero_map_marked")
+        return n.value

@@ -326,6 +326,17 @@ typedef struct gsx_state_view {
 int gsx_import_state(gsx_engine* e, const gsx_state_view* s);
 int gsx_export_state(gsx_engine* e, gsx_state_view* s);
 
+/* A consistency check of the engine's zero map (per 64-pair tile,
+ * topic and penalty counter, "every present pair holds +0.0", which lets the
+ * refresh pass skip the counter's load): *n = the entries that say zero while
+ * a present pair holds another bit pattern.  Always 0; a test hook and a
+ * debugging aid. */
+int gsx_zero_map_violations(gsx_engine* e, uint64_t* n);
+/* *n = the entries of the zero map that say "maybe non-zero": 0 after a load;
+ * a store of a non-zero penalty counter marks its tile's entry, a refresh that
+ * finds the whole tile back at +0.0 clears it. */
+int gsx_zero_map_marked(gsx_engine* e, uint64_t* n);
+
 /* WithPeerScoreInspect's extended view (ExtendedPeerScoreInspectFn,
  * inspectScoresExtended score.go:463-493): a PeerScoreSnapshot per pair
  * whose observer keeps peerStats for the peer (present = 1), its
