@@ -370,6 +370,13 @@ hipError_t launch_prop_fold(const PropState& ps, const DevState& s, uint32_t* fi
                             hipStream_t st);
 hipError_t launch_prop_from(const PropState& ps, int32_t* first_from, hipStream_t st);
 hipError_t launch_prop_hops_export(const PropState& ps, uint8_t* hop_mn, hipStream_t st);
+// gsx_prop_stats (gsx_prop_stats.hip): the same hops as launch_prop_hops_export's,
+// counted instead of written.  msg_hop_hist [n_msgs][PROP_STATS_HOPS] += nodes per
+// (message, hop); node_received [n_nodes] += messages at hops >= 1, node_hop_sum
+// their hops (either may be null).  The caller zeroes the outputs.
+constexpr uint32_t PROP_STATS_HOPS = 65;  // GSX_MAX_HOPS + 1
+hipError_t launch_prop_stats(const PropState& ps, uint32_t* msg_hop_hist, uint32_t* node_received,
+                             unsigned long long* node_hop_sum, hipStream_t st);
 // The call's arrival hops as the validation-code planes of its message set
 // (VcRef: [plane][node][word], n_planes <= 8; hist rows 1 .. n_rows - 1).
 hipError_t launch_prop_vcodes(const PropState& ps, uint64_t* vc, uint32_t n_planes, hipStream_t st);

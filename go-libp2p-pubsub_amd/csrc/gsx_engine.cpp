@@ -407,6 +407,12 @@ struct gsx_engine {
         uint64_t* vcnt = nullptr;      // per node: forwarded-set sizes (late duplicate accounting)
         uint64_t halo_cap = 0, hfrom_cap = 0;
         unsigned long long* dcount = nullptr;
+        // gsx_prop_stats: the device side of results that go to host memory (the
+        // histogram grown when m grows, the per-node arrays sized once)
+        uint32_t* st_hist = nullptr;
+        size_t st_hist_cap = 0;
+        uint32_t* st_recv = nullptr;
+        unsigned long long* st_sum = nullptr;
     } prop;
     bool prop_track = true;  // gsx_prop_set_tracking: keep first-deliverer rows (gsx_prop_results)
 
@@ -892,7 +898,8 @@ void free_state(gsx_engine* e) {
                   e->prop.cent, e->prop.cend, e->prop.chg, e->prop.nchg, e->prop.ndirty, e->prop.rfwd,
                   e->d_halo_pair, e->d_send_slot, e->d_rmark_v, e->d_rmark_u, e->prop.front_g, e->prop.occ_g,
                   e->prop.src_bits, e->prop.src_ids, e->prop.src_rows,
-                  e->prop.d_dig, e->prop.rcand, e->prop.tterm, e->prop.tgen, e->prop.hist_alt, e->prop.occ_alt};
+                  e->prop.d_dig, e->prop.rcand, e->prop.tterm, e->prop.tgen, e->prop.hist_alt, e->prop.occ_alt,
+                  e->prop.st_hist, e->prop.st_recv, e->prop.st_sum};
     for (void* p : pp)
         if (p) (void)hipFree(p);
     std::vector<hipEvent_t> evs = std::move(e->prop.ev);
@@ -3804,6 +3811,66 @@ int gsx_prop_results(gsx_engine* e, uint8_t* hop, int32_t* first_from) {
         (void)hipFree(d_ff);
     }
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GSX_OK;
+}
+
+int gsx_prop_stats(gsx_engine* e, uint32_t* msg_hop_hist, uint32_t* node_received, uint64_t* node_hop_sum) {
+    static_assert(gsx::PROP_STATS_HOPS == GSX_MAX_HOPS + 1, "one histogram column per hop 0 .. GSX_MAX_HOPS");
+    if (!e) return GSX_EINVAL;
+    auto& P = e->prop;
+    if (!P.have_last) return fail(e, GSX_ESTATE, "no propagation call yet");
+    if (P.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
+    gsx::PropState ps = P.last;
+    ps.n_rows = P.rows_valid;
+    const size_t m = ps.n_msgs, N = ps.n_nodes;
+    if (m == 0 || N == 0 || (!msg_hop_hist && !node_received && !node_hop_sum)) return GSX_OK;
+    const size_t cells = m * gsx::PROP_STATS_HOPS;
+    // device memory is written in place, in stream order; host memory gets a copy of the engine's buffers
+    const bool hist_dev = msg_hop_hist && on_device(msg_hop_hist);
+    const bool recv_dev = node_received && on_device(node_received);
+    const bool sum_dev = node_hop_sum && on_device(node_hop_sum);
+    if (!hist_dev && P.st_hist_cap < cells) {  // (the kernel always counts the histogram)
+        if (P.st_hist) {
+            HIPCHK(e, hipStreamSynchronize(e->stream));
+            (void)hipFree(P.st_hist);
+        }
+        P.st_hist = nullptr;
+        P.st_hist_cap = 0;
+        if (int rc = dalloc(e, &P.st_hist, cells)) return rc;
+        P.st_hist_cap = cells;
+    }
+    if (node_received && !recv_dev && !P.st_recv)
+        if (int rc = dalloc(e, &P.st_recv, N)) return rc;
+    if (node_hop_sum && !sum_dev && !P.st_sum)
+        if (int rc = dalloc(e, &P.st_sum, N)) return rc;
+    uint32_t* d_hist = hist_dev ? msg_hop_hist : P.st_hist;
+    uint32_t* d_recv = !node_received ? nullptr : recv_dev ? node_received : P.st_recv;
+    unsigned long long* d_sum =
+        !node_hop_sum ? nullptr : sum_dev ? reinterpret_cast<unsigned long long*>(node_hop_sum) : P.st_sum;
+    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
+    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    HIPCHK(e, hipMemsetAsync(d_hist, 0, 4 * cells, e->stream));
+    if (d_recv) HIPCHK(e, hipMemsetAsync(d_recv, 0, 4 * N, e->stream));
+    if (d_sum) HIPCHK(e, hipMemsetAsync(d_sum, 0, 8 * N, e->stream));
+    HIPCHK(e, gsx::launch_prop_stats(ps, d_hist, d_recv, d_sum, e->stream));
+    if (region) {
+        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
+        ++e->t_used;
+    }
+    bool host = false;
+    if (msg_hop_hist && !hist_dev) {
+        HIPCHK(e, hipMemcpyAsync(msg_hop_hist, d_hist, 4 * cells, hipMemcpyDeviceToHost, e->stream));
+        host = true;
+    }
+    if (node_received && !recv_dev) {
+        HIPCHK(e, hipMemcpyAsync(node_received, d_recv, 4 * N, hipMemcpyDeviceToHost, e->stream));
+        host = true;
+    }
+    if (node_hop_sum && !sum_dev) {
+        HIPCHK(e, hipMemcpyAsync(node_hop_sum, d_sum, 8 * N, hipMemcpyDeviceToHost, e->stream));
+        host = true;
+    }
+    if (host) HIPCHK(e, hipStreamSynchronize(e->stream));
     return GSX_OK;
 }
 

@@ -423,6 +423,8 @@ SIGNATURES = {
     "gsx_synthesize_state": (C.c_int, [C.c_void_p, P(SynthSpec)]),
     "gsx_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, P(PropConfig), P(PropOut)]),
     "gsx_prop_results": (C.c_int, [C.c_void_p, P(C.c_uint8), P(C.c_int32)]),
+    # (host or device pointers, like gsx_prop_pending_credits: passed as addresses)
+    "gsx_prop_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsx_prop_set_tracking": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_prop_duplicates": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_size_t]),
     "gsx_set_pair_ips": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint32), C.c_size_t]),

@@ -43,6 +43,81 @@ def make_struct(cls, **kw):
     return s
 
 
+class PropStats:
+    """Per-message delivery and latency summary of a propagation call
+    (gsx_prop_stats): hop_hist[k, h] = nodes that first got message k at hop
+    h (h = 0: its source); optionally node_received[u] = messages node u got
+    at hops >= 1 and node_hop_sum[u] = the sum of their hops.  Everything
+    below is numpy on those integers; nothing here touches the device."""
+
+    def __init__(self, hop_hist, node_received=None, node_hop_sum=None):
+        self.hop_hist = np.ascontiguousarray(hop_hist, dtype=np.uint32).reshape(-1, abi.GSX_MAX_HOPS + 1)
+        self.node_received = None if node_received is None else np.ascontiguousarray(node_received, dtype=np.uint32)
+        self.node_hop_sum = None if node_hop_sum is None else np.ascontiguousarray(node_hop_sum, dtype=np.uint64)
+
+    @property
+    def n_msgs(self) -> int:
+        return self.hop_hist.shape[0]
+
+    def _h(self) -> np.ndarray:
+        return self.hop_hist.astype(np.int64)
+
+    def reached(self) -> np.ndarray:
+        """[m] i64: nodes that received each message (first receipts, hops >= 1; the source is not one)."""
+        return self._h()[:, 1:].sum(1)
+
+    def delivery_ratio(self, n_receivers) -> np.ndarray:
+        """[m] f64: reached() / n_receivers (a count, or one per message: e.g. the topic's subscribers - 1)."""
+        return self.reached() / np.asarray(n_receivers, dtype=np.float64)
+
+    def last_hop(self) -> np.ndarray:
+        """[m] i64: the last hop at which a node got the message (0: only its source holds it; -1: an
+        empty row, e.g. a shard that holds neither the source nor a receiver)."""
+        nz = self.hop_hist != 0
+        last = nz.shape[1] - 1 - np.argmax(nz[:, ::-1], axis=1)
+        return np.where(nz.any(1), last, -1).astype(np.int64)
+
+    def mean_hop(self) -> np.ndarray:
+        """[m] f64: mean arrival hop over the message's receivers (nan: nobody received it)."""
+        h = self._h()
+        tot = (h[:, 1:] * np.arange(1, h.shape[1])).sum(1)
+        r = h[:, 1:].sum(1)
+        return np.where(r > 0, tot / np.maximum(r, 1), np.nan)
+
+    def hops_to_fraction(self, q: float, n_receivers) -> np.ndarray:
+        """[m] i64: the smallest hop h after which at least a fraction q of n_receivers holds the
+        message (receipts of hops 1 .. h over n_receivers >= q); -1 if the call never got there."""
+        cum = np.cumsum(self._h(), axis=1)
+        cum -= cum[:, :1]  # hop 0 is the source, not a receipt
+        ok = cum / np.asarray(n_receivers, dtype=np.float64).reshape(-1, 1) >= q
+        return np.where(ok.any(1), np.argmax(ok, axis=1), -1).astype(np.int64)
+
+    def node_mean_hop(self) -> np.ndarray:
+        """[n] f64: mean arrival hop per node (nan: the node received nothing); needs per_node."""
+        r = self.node_received.astype(np.float64)
+        return np.where(r > 0, self.node_hop_sum.astype(np.float64) / np.maximum(r, 1), np.nan)
+
+    def __add__(self, other: "PropStats") -> "PropStats":
+        """Range shards of one call, in rank order: the histograms add up (each node is on one
+        shard), the per-node arrays (kept when both sides have them) follow one another."""
+        if self.hop_hist.shape != other.hop_hist.shape:
+            raise ValueError("histograms of different calls")
+        tot = self._h() + other._h()
+        both = self.node_received is not None and other.node_received is not None
+        return PropStats(tot, np.concatenate([self.node_received, other.node_received]) if both else None,
+                         np.concatenate([self.node_hop_sum, other.node_hop_sum]) if both else None)
+
+    @staticmethod
+    def concat(parts) -> "PropStats":
+        """Message-parallel replicas, in rank order: each holds the rows of its message slice over
+        every node, so the rows follow one another and the per-node arrays add up."""
+        parts = list(parts)
+        per_node = bool(parts) and all(p.node_received is not None for p in parts)
+        return PropStats(np.concatenate([p.hop_hist for p in parts], 0) if parts else np.zeros((0, 65), np.uint32),
+                         sum(p.node_received.astype(np.uint64) for p in parts) if per_node else None,
+                         sum(p.node_hop_sum for p in parts) if per_node else None)
+
+
 class Engine:
     def __init__(self, n_topics: int, device: int = 0):
         self.lib = abi.load_library()
@@ -385,6 +460,27 @@ class Engine:
         frm = np.empty((n_msgs, self.n_nodes), dtype=np.int32) if self._track else None
         self._chk(self.lib.gsx_prop_results(self.h, _ptr(hop, C.c_uint8), _ptr(frm, C.c_int32)), "gsx_prop_results")
         return hop, frm
+
+    def prop_stats(self, n_msgs: int, per_node: bool = False, out_ptrs=None):
+        """gsx_prop_stats of the last propagation (n_msgs: its messages) -> PropStats:
+        hop_hist [m, GSX_MAX_HOPS + 1] u32 and, with per_node, node_received
+        [n_local] u32 and node_hop_sum [n_local] u64.
+
+        out_ptrs = (hist, received, hop_sum): device pointers or tensors (None /
+        0 skips one) written in stream order with no host sync, as
+        pending_credits takes them; then -> None."""
+        if out_ptrs is not None:
+            self._chk(self.lib.gsx_prop_stats(self.h, *[self._p(p) if p is not None else None for p in out_ptrs]),
+                      "gsx_prop_stats")
+            return None
+        hist = np.zeros((n_msgs, abi.GSX_MAX_HOPS + 1), dtype=np.uint32)
+        recv = np.zeros(self.n_nodes, dtype=np.uint32) if per_node else None
+        hsum = np.zeros(self.n_nodes, dtype=np.uint64) if per_node else None
+        self._chk(self.lib.gsx_prop_stats(self.h, C.c_void_p(hist.ctypes.data if hist.size else None),
+                                          C.c_void_p(recv.ctypes.data if per_node and recv.size else None),
+                                          C.c_void_p(hsum.ctypes.data if per_node and hsum.size else None)),
+                  "gsx_prop_stats")
+        return PropStats(hist, recv, hsum)
 
     def pending_credits(self, first_ptr: int, dup_ptr: int):
         """Copy the pending (GSX_CREDIT_DEFER) counts to caller memory (host or device pointers)."""

@@ -287,6 +287,27 @@ class RangeSharded:
         out = be.prop_end()
         return out_dict(out), totals(out, tp)
 
+    def prop_stats(self, n_msgs: int, per_node: bool = False):
+        """gsx_prop_stats of the last propagate() over the whole overlay -> PropStats: every rank
+        writes the histogram of its nodes into a device tensor (no host sync), one all-reduce
+        sums them (as int64: torch reduces no unsigned 32-bit integers).  per_node: this
+        rank's node_received / node_hop_sum as well; they stay per rank."""
+        torch = _torch()
+        from .engine import PropStats
+
+        with self._on_stream():
+            dev = self.tp.device
+            h32 = torch.zeros((n_msgs, abi.GSX_MAX_HOPS + 1), dtype=torch.int32, device=dev)
+            n_local = self.be.n_nodes if per_node else 0
+            recv = torch.zeros(n_local, dtype=torch.int32, device=dev) if per_node else None
+            hsum = torch.zeros(n_local, dtype=torch.int64, device=dev) if per_node else None
+            self.be.prop_stats(n_msgs, out_ptrs=(h32, recv, hsum))
+            h = h32.to(torch.int64) & 0xFFFFFFFF  # (the u32 counts, whatever their top bit)
+            self.tp.all_reduce_sum(h)
+            return PropStats(h.cpu().numpy(),
+                             recv.cpu().numpy().view(np.uint32) if per_node else None,
+                             hsum.cpu().numpy().view(np.uint64) if per_node else None)
+
 
     def _propagate_rep(self, W, cfg) -> int:
         """The replicated frontier (gsx.h gsx_prop_rep_*): the cross pairs' fwd
@@ -640,6 +661,32 @@ class MessageParallel:
                 if not self.epoch:
                     self.end_epoch()
             return out_dict(out), tot
+
+    def prop_stats(self, n_msgs: int, per_node: bool = False):
+        """gsx_prop_stats of the last propagate() of n_msgs messages -> PropStats of the whole batch:
+        every replica holds the histogram rows of its bounds(n_msgs) slice; one all-gather (rows
+        padded to the largest slice) gives the full [m, hops] table.  per_node: the per-node
+        arrays summed over the replicas (each counted its own messages at every node)."""
+        torch = _torch()
+        from .engine import PropStats
+
+        with self._on_stream():
+            dev, w = self.tp.device, self.tp.world
+            counts = [(n_msgs * (k + 1)) // w - (n_msgs * k) // w for k in range(w)]
+            h32 = torch.zeros((max(counts + [0]), abi.GSX_MAX_HOPS + 1), dtype=torch.int32, device=dev)
+            n = self.e.n_nodes if per_node else 0
+            recv = torch.zeros(n, dtype=torch.int32, device=dev) if per_node else None
+            hsum = torch.zeros(n, dtype=torch.int64, device=dev) if per_node else None
+            if counts[self.tp.rank]:
+                self.e.prop_stats(counts[self.tp.rank], out_ptrs=(h32, recv, hsum))
+            parts = self.tp.all_gather(h32)
+            table = torch.cat([parts[k][: counts[k]] for k in range(w)], 0).cpu().numpy().view(np.uint32)
+            if not per_node:
+                return PropStats(table)
+            nd = torch.stack([recv.to(torch.int64) & 0xFFFFFFFF, hsum])
+            self.tp.all_reduce_sum(nd)
+            nd = nd.cpu().numpy()
+            return PropStats(table, nd[0], nd[1].view(np.uint64))
 
     def _merge_cache(self, msgs, cfg, n_mine: int):
         """One all-gather of the replicas' cache blocks; every replica Puts the whole batch."""

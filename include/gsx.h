@@ -490,6 +490,30 @@ int gsx_propagate(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_c
  * none), laid out [message][node] over this engine's nodes.  Either pointer
  * may be NULL. */
 int gsx_prop_results(gsx_engine* e, uint8_t* hop, int32_t* first_from);
+/* Per-message and per-node summaries of the last propagation, reduced on the
+ * device from the state gsx_prop_results reads, without the [message][node]
+ * export.  With hop(k, u) the byte gsx_prop_results writes for message k and
+ * this engine's node u:
+ *   msg_hop_hist[k * (GSX_MAX_HOPS + 1) + h]  nodes u with hop(k, u) == h (the
+ *                     nodes the message never reached: nodes - the row's sum),
+ *   node_received[u]  messages k with 1 <= hop(k, u) <= GSX_MAX_HOPS (a node's
+ *                     own messages, hop 0, are not counted),
+ *   node_hop_sum[u]   the sum of hop(k, u) over those messages (mean arrival
+ *                     hop of a node: node_hop_sum / node_received).
+ * msg_hop_hist has n_msgs * (GSX_MAX_HOPS + 1) entries for the last call's
+ * n_msgs, the per-node arrays one per node of this engine.  Every pointer
+ * may be NULL (that output is skipped) and may be host or device memory:
+ * device memory is written in stream order with no host synchronisation
+ * (range shards all-reduce the histograms: the sum over ranks is the whole
+ * overlay's), host memory is complete when the call returns.  Works after
+ * gsx_propagate and after gsx_prop_begin .. gsx_prop_end, on unsharded
+ * engines and range shards (a shard: its own nodes), for every router, with
+ * or without first-deliverer tracking.  GSX_ESTATE before any propagation
+ * call and while a stepped call is in flight; a call of no messages, or an
+ * engine of no nodes, writes nothing.  All integer sums: the result is
+ * bit-identical from run to run.  Inside a gsx_timing_begin region the
+ * call's device work counts as one timed launch. */
+int gsx_prop_stats(gsx_engine* e, uint32_t* msg_hop_hist, uint32_t* node_received, uint64_t* node_hop_sum);
 /* Duplicate receipts of the last propagation (the copies pushMsg traces as
  * DuplicateMessage, pubsub.go:1046-1060 -> trace.go:136-164): rows[pair *
  * n_words + w] bit b is set when the pair's neighbour sent its observer a
