@@ -48,7 +48,7 @@ struct KernParams {
 // Records (one per observer, peer, topic: the reference's topicStats,
 // score.go:37-62) are tiled by 64 pairs — one wavefront's lanes:
 //   rec   [p/64][t][field][64]  8-byte fields, field = FMD, MMD, MFP, IMD, GRAFT
-//   rflag [p/64][t][64]         u8: IN_MESH | ACTIVE | FRESH
+//   rflag [p/64][t][64]         u8: IN_MESH | ACTIVE | FRESH | write-back epoch (2 bits)
 // so the lanes of a wave read each field of a topic as one contiguous 512-B
 // span and a wave's whole working set (T x 2.6 KB) is one contiguous block
 // of HBM.  meshTime is not stored: for an in-mesh record it is
@@ -100,11 +100,24 @@ struct DevState {
     uint64_t n_pairs;
     uint32_t n_topics;
     int64_t last_refresh;  // time of the last refreshScores() (derives meshTime)
+    // Deferred write-back of the decayed counters (REC_EPOCH below): refreshes
+    // since the last one that stored them (0 .. wb_period - 1), the period
+    // (1, 2 or 4 refreshes; 1 = every refresh stores), and DecayToZero.
+    uint32_t phase;
+    uint32_t wb_period;
+    double decay_to_zero;
 };
 
 constexpr uint8_t REC_IN_MESH = 0x01;
 constexpr uint8_t REC_ACTIVE = 0x02;
 constexpr uint8_t REC_FRESH = 0x04;  // grafted since the last refresh that covered it: meshTime == 0
+// The write-back epoch of a record: its stored fmd / mmd / mfp / imd are its
+// values as of the refresh at which DevState::phase was this value.  A
+// connected pair's scored record has (phase - epoch) & 3 decays pending
+// (rec_pend, gsx_ops.h); a disconnected pair is never decayed (score.go:503-516)
+// and an unscored topic's record neither, so theirs are always current.
+constexpr uint8_t REC_EPOCH = 0x18;
+constexpr int REC_EPOCH_SHIFT = 3;
 constexpr uint8_t PAIR_PRESENT = 0x01;
 constexpr uint8_t PAIR_CONNECTED = 0x02;
 constexpr uint32_t IPG_NONE = 0xFFFFFFFFu;
@@ -919,6 +932,9 @@ hipError_t launch_score_subset(const DevState& s, const KernParams& kp, const ui
 hipError_t launch_apply_events(const DevState& s, const DevPeerParams& pp, const DevEvent* ev,
                                const uint32_t* group_off, uint32_t n_groups, hipStream_t st);
 hipError_t launch_recap(const DevState& s, uint32_t topic, double cap2, double cap3, hipStream_t st);
+// Applies every record's pending decays, stores the counters and clears every
+// epoch; the caller then sets phase = 0.
+hipError_t launch_materialize(const DevState& s, hipStream_t st);
 // The drop-in round trip (k_dropin): events + score() of the pairs they change
 // (prs; the whole row of the observers in obs: AddPeer / RemovePeer move their
 // IP colocation counts) into the device vector and the host-mapped copy, then

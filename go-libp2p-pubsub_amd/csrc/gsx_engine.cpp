@@ -80,6 +80,11 @@ struct gsx_engine {
     uint32_t n_nodes = 0;
     uint64_t E = 0, rs = 0, n_tiles = 0;
     int64_t last_refresh = 0;  // now of the last refreshScores() pass
+    // Deferred write-back of the decayed counters (gsx_set_decay_writeback):
+    // the refresh pass stores them every wb_period-th refresh; phase counts the
+    // refreshes since the last one that did (DevState::phase, REC_EPOCH).
+    uint32_t phase = 0;
+    uint32_t wb_period = 4;
     std::vector<int64_t> row_ptr;
     std::vector<int32_t> col_host;
     std::vector<uint32_t> pair_obs;
@@ -592,7 +597,20 @@ gsx::DevState dev_state(const gsx_engine* e) {
     s.n_pairs = e->E;
     s.n_topics = e->T;
     s.last_refresh = e->last_refresh;
+    s.phase = e->phase;
+    s.wb_period = e->wb_period;
+    s.decay_to_zero = e->pp.decay_to_zero;
     return s;
+}
+
+// Every record's pending decays applied and stored, the phase restarted: before
+// anything that changes the decay parameters or the write-back period (the
+// pending decays are owed under the old ones).
+int materialize_all(gsx_engine* e) {
+    if (!e->loaded) return GSX_OK;
+    HIPCHK(e, gsx::launch_materialize(dev_state(e), e->stream));
+    e->phase = 0;
+    return GSX_OK;
 }
 
 gsx::DevPeerParams dev_peer_params(const gsx_engine* e) {
@@ -1492,6 +1510,7 @@ int gsx_set_peer_params(gsx_engine* e, const gsx_peer_score_params* p) {
     if (!e || !p) return GSX_EINVAL;
     int rc = flush(e);  // queued events see the params they were issued under
     if (rc) return rc;
+    if ((rc = materialize_all(e))) return rc;  // (DecayToZero of the pending decays)
     e->pp = *p;
     e->pp_set = true;
     e->invalidate_scores();
@@ -1515,6 +1534,7 @@ int gsx_set_topic_params(gsx_engine* e, uint32_t topic, const gsx_topic_score_pa
     if (int rc = fold_deferred(e)) return rc;
     int rc = flush(e);
     if (rc) return rc;
+    if ((rc = materialize_all(e))) return rc;  // (the decay constants and `scored` of the pending decays)
     const bool exist = e->scored[topic];
     const gsx_topic_score_params old = e->tp[topic];
     e->tp[topic] = *p;
@@ -1599,6 +1619,7 @@ int load_overlay(gsx_engine* e, uint32_t n_total, uint32_t node_lo, uint32_t n_n
     e->rs = (E + 63) & ~uint64_t(63);
     e->n_tiles = (E + gsx::TILE - 1) / gsx::TILE;
     e->last_refresh = 0;
+    e->phase = 0;
     e->row_ptr.assign(row_ptr, row_ptr + n_nodes + 1);
     e->col_host.assign(col, col + E);
     e->pair_obs.resize(E);
@@ -2120,6 +2141,18 @@ int gsx_refresh(gsx_engine* e, int64_t now) {
     e->scores_exact();
     e->state_changed();
     e->last_refresh = now;
+    e->phase = e->phase + 1 >= e->wb_period ? 0 : e->phase + 1;  // (the pass stored the counters at 0)
+    return GSX_OK;
+}
+
+int gsx_set_decay_writeback(gsx_engine* e, uint32_t k) {
+    if (!e) return GSX_EINVAL;
+    if (k != 1 && k != 2 && k != 4) return fail(e, GSX_EINVAL, "decay write-back period must be 1, 2 or 4");
+    if (int rc = gx_busy(e)) return rc;
+    if (int rc = fold_deferred(e)) return rc;
+    if (int rc = flush(e)) return rc;
+    if (int rc = materialize_all(e)) return rc;
+    e->wb_period = k;
     return GSX_OK;
 }
 
@@ -2390,6 +2423,7 @@ int gsx_import_state(gsx_engine* e, const gsx_state_view* s) {
     const size_t E = e->E, R = (size_t)e->T * E;
     if (int rc = ensure_tmp(e)) return rc;
     e->last_refresh = s->last_refresh_ns;
+    e->phase = 0;  // every record and flag byte is overwritten: nothing pends, the epochs are 0
     const gsx::DevState ds = dev_state(e);
     const void* fields[gsx::NFIELD] = {s->first_message_deliveries, s->mesh_message_deliveries,
                                        s->mesh_failure_penalty, s->invalid_message_deliveries, s->graft_time_ns};
@@ -2438,6 +2472,7 @@ int gsx_synthesize_state(gsx_engine* e, const gsx_synth_spec* sp) {
     d.expire_jitter = sp->expire_jitter_ns;
     d.sybil_first = sp->sybil_first_node;
     e->last_refresh = sp->now_ns;  // meshTime = now - graftTime for every in-mesh record
+    e->phase = 0;                  // (every record and flag byte is overwritten)
     const gsx::DevState s = dev_state(e);
     HIPCHK(e, gsx::launch_synthesize(s, e->d_col, d, e->stream));
     HIPCHK(e, gsx::launch_rebuild_ipcount(s, e->n_groups, e->stream));

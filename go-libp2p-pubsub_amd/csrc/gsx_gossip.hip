@@ -268,12 +268,13 @@ __device__ __forceinline__ void gx_credit(const DevState& s, uint64_t q, uint32_
     if (!(k1 | k2 | k4) || !scored_topic(s, q, t)) return;
     const DevTopicParams& tp = s.tp[t];
     const size_t b = rec_index(q, t, s.n_topics, FMD);
+    const uint8_t fl = rec_materialize(s, q, t);
     if (k4) {
         zmap_mark(s, q, t, IMD);
         s.rec[b + IMD * TILE] = add_ones_capped(s.rec[b + IMD * TILE], k4, __builtin_inf());
     }
     if (k1) s.rec[b + FMD * TILE] = add_ones_capped(s.rec[b + FMD * TILE], k1, tp.cap2);
-    if ((k1 | k2) && (s.rflags[flag_index(q, t, s.n_topics)] & REC_IN_MESH))
+    if ((k1 | k2) && (fl & REC_IN_MESH))
         s.rec[b + MMD * TILE] = add_ones_capped(s.rec[b + MMD * TILE], k1 + k2, tp.cap3);
 }
 

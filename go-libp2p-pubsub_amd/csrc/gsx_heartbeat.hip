@@ -405,7 +405,8 @@ __device__ __forceinline__ void apply_events(const DevState& s, const HbState& h
     if (f & ST_GRAFT) {  // ev_graft (a grafted candidate is present)
         if (scored) {
             reinterpret_cast<int64_t*>(s.rec)[rec_index(r, t, s.n_topics, GRAFT)] = h.now;
-            s.rflags[flag_index(r, t, s.n_topics)] = REC_IN_MESH | REC_FRESH;
+            const size_t fi = flag_index(r, t, s.n_topics);  // (the counters' epoch stays)
+            s.rflags[fi] = (uint8_t)((s.rflags[fi] & REC_EPOCH) | REC_IN_MESH | REC_FRESH);
         }
         atomicOr((unsigned long long*)&h.ctl[2 * (size_t)r], 1ull << t);
     }
@@ -413,6 +414,7 @@ __device__ __forceinline__ void apply_events(const DevState& s, const HbState& h
         if (scored) {
             // after a graft in the same unit the record is fresh (not active)
             const bool active = (f & ST_ACTIVE) && !(f & ST_GRAFT);
+            const uint8_t ep = rec_materialize(s, r, t) & REC_EPOCH;
             if (active) {
                 const size_t b = rec_index(r, t, s.n_topics, FMD);
                 const double threshold = s.tp[t].thr3;
@@ -423,7 +425,7 @@ __device__ __forceinline__ void apply_events(const DevState& s, const HbState& h
                     s.rec[b + MFP * TILE] = s.rec[b + MFP * TILE] + deficit * deficit;
                 }
             }
-            s.rflags[flag_index(r, t, s.n_topics)] = active ? REC_ACTIVE : 0;
+            s.rflags[flag_index(r, t, s.n_topics)] = (active ? REC_ACTIVE : 0) | ep;
         }
         add_backoff(h, r, t, h.gp.prune_backoff_ns);
         atomicOr((unsigned long long*)&h.ctl[2 * (size_t)r + 1], 1ull << t);

@@ -68,6 +68,14 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
     const DevPeerParams& pp = kp.pp;
     // Disconnected (retained) peers are not decayed (:503-516).
     const bool conn = REFRESH && (st & PAIR_CONNECTED);
+    // Deferred write-back (REC_EPOCH, gsx_device.h): the decayed counters are
+    // stored only by the refresh that completes a period; the others keep them
+    // in registers for the score and leave the stored values `pend` decays
+    // behind, which every pass applies first (a masked score pass applies just
+    // those).  Disconnected pairs are never decayed: nothing is pending there.
+    const uint32_t phase = s.phase;
+    const bool wb = REFRESH && phase + 1 >= s.wb_period;
+    const bool lag = st & PAIR_CONNECTED;
     double* const tile = s.rec + (p / TILE) * (uint64_t)T * (NFIELD * TILE) + lane;
     uint8_t* const ftile = s.rflags + (p / TILE) * (uint64_t)T * TILE + lane;
     double score = 0.0;
@@ -77,21 +85,30 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
                           int64_t graft, uint8_t fl, uint32_t zmt) {
         double* const r = tile + (uint64_t)t * (NFIELD * TILE);
         int64_t mt = 0;
-        if (conn) {
-            // a counter that decays stays written back only if it changed: a
-            // zero counter (most peers never send an invalid message, most
-            // meshes never fail) decays to itself, and a wave whose 64 lanes
-            // all hold zero skips the 512-B store entirely
-            const double fmd0 = fmd, mmd0 = mmd, mfp0 = mfp, imd0 = imd;
+        const double fmd0 = fmd, mmd0 = mmd, mfp0 = mfp, imd0 = imd;
+        // the pending decays, and this refresh's: the same multiply and compare
+        // in the same order as a store after each would have seen (wave-uniform
+        // bound unless an event touched a lane's record since the last store)
+        const uint32_t nd = (lag ? (phase - ((uint32_t)fl >> REC_EPOCH_SHIFT)) & 3u : 0u) + (conn ? 1u : 0u);
+        for (uint32_t i = 0; i < nd; ++i) {
             fmd = decay(fmd, tp.d2, pp.decay_to_zero);
             mmd = decay(mmd, tp.d3, pp.decay_to_zero);
             mfp = decay(mfp, tp.d3b, pp.decay_to_zero);
             imd = decay(imd, tp.d4, pp.decay_to_zero);
-            if (__double_as_longlong(fmd) != __double_as_longlong(fmd0)) __builtin_nontemporal_store(fmd, r + FMD * TILE);
-            if (__double_as_longlong(mmd) != __double_as_longlong(mmd0)) __builtin_nontemporal_store(mmd, r + MMD * TILE);
-            if (__double_as_longlong(mfp) != __double_as_longlong(mfp0)) __builtin_nontemporal_store(mfp, r + MFP * TILE);
-            if (__double_as_longlong(imd) != __double_as_longlong(imd0)) __builtin_nontemporal_store(imd, r + IMD * TILE);
+        }
+        if (conn) {
             uint8_t nf = fl & ~REC_FRESH;
+            if (wb) {
+                // a counter that decays is written back only if it changed: a
+                // zero counter (most peers never send an invalid message, most
+                // meshes never fail) decays to itself, and a wave whose 64 lanes
+                // all hold zero skips the 512-B store entirely
+                if (__double_as_longlong(fmd) != __double_as_longlong(fmd0)) __builtin_nontemporal_store(fmd, r + FMD * TILE);
+                if (__double_as_longlong(mmd) != __double_as_longlong(mmd0)) __builtin_nontemporal_store(mmd, r + MMD * TILE);
+                if (__double_as_longlong(mfp) != __double_as_longlong(mfp0)) __builtin_nontemporal_store(mfp, r + MFP * TILE);
+                if (__double_as_longlong(imd) != __double_as_longlong(imd0)) __builtin_nontemporal_store(imd, r + IMD * TILE);
+                nf &= ~REC_EPOCH;  // stored as of the new phase, 0
+            }
             if (fl & REC_IN_MESH) {  // :544-549
                 mt = now - graft;
                 if (mt > tp.act3) nf |= REC_ACTIVE;
@@ -103,11 +120,19 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
         }
         if constexpr (REFRESH) {
             // a marked counter that is +0.0 again in all 64 pairs of the tile
-            // (all present: no lane returned above): one lane clears the mark
+            // (all present: no lane returned above): one lane clears the mark.
+            // The mark speaks of what is stored, so a refresh that does not
+            // write back first stores the zeros of the lanes whose stored value
+            // is not yet zero: +0.0 decays to itself, so a stored zero is the
+            // record's value under any number of pending decays and the
+            // record's epoch need not move.  (Once per tile and counter that
+            // runs out, not a per-step store.)
             if (zmt && __ballot(1) == ~0ull) {
                 uint8_t* const zb = s.zmap + zoff + 2 * t;
                 const bool z3 = (zmt & ZM_MFP_BITS) && __ballot(__double_as_longlong(mfp) != 0) == 0;
                 const bool z4 = (zmt & ZM_IMD_BITS) && __ballot(__double_as_longlong(imd) != 0) == 0;
+                if (z3 && !wb && __double_as_longlong(mfp0) != 0) r[MFP * TILE] = 0.0;
+                if (z4 && !wb && __double_as_longlong(imd0) != 0) r[IMD * TILE] = 0.0;
                 if (z3 && lane == 0) zb[0] = ZM_ZERO;
                 if (z4 && lane == 0) zb[1] = ZM_ZERO;
             }
@@ -254,7 +279,8 @@ __global__ __launch_bounds__(256) void k_gather_scores(const double* __restrict_
         out[i] = score[pairs[i]];
 }
 
-// SetTopicScoreParams recap (score.go:217-231)
+// SetTopicScoreParams recap (score.go:217-231).  The setter runs k_materialize
+// first (the decay constants change with the caps), so no decay is pending here.
 __global__ __launch_bounds__(256) void k_recap(DevState s, uint32_t topic, double cap2, double cap3) {
     const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (p >= s.n_pairs || !(s.pflags[p] & PAIR_PRESENT)) return;
@@ -292,9 +318,16 @@ __global__ __launch_bounds__(256) void k_untile_field(DevState s, int field, voi
     if (p >= s.n_pairs) return;
     const size_t i = (size_t)t * s.n_pairs + p;
     const bool present = s.pflags[p] & PAIR_PRESENT;  // no peerStats: no topicStats either (export zeros)
-    if (field < NFIELD)
+    if (field == GRAFT)
         static_cast<double*>(dst)[i] = present ? s.rec[rec_index(p, t, s.n_topics, field)] : 0.0;
-    else
+    else if (field < NFIELD) {  // a counter: with its pending decays (the caller sees every refresh's result)
+        double v = 0.0;
+        if (present) {
+            const RecVals r = rec_read(s, p, t);
+            v = field == FMD ? r.fmd : field == MMD ? r.mmd : field == MFP ? r.mfp : r.imd;
+        }
+        static_cast<double*>(dst)[i] = v;
+    } else
         static_cast<uint8_t*>(dst)[i] =
             present ? (s.rflags[flag_index(p, t, s.n_topics)] & (REC_IN_MESH | REC_ACTIVE)) : 0;
 }
@@ -502,6 +535,26 @@ hipError_t launch_gather_scores(const double* score, const uint64_t* pairs, uint
 hipError_t launch_recap(const DevState& s, uint32_t topic, double cap2, double cap3, hipStream_t st) {
     if (s.n_pairs == 0) return hipSuccess;
     hipLaunchKernelGGL(k_recap, dim3(blocks_for(s.n_pairs, 256)), dim3(256), 0, st, s, topic, cap2, cap3);
+    return hipGetLastError();
+}
+
+// Every record brought up to date and every epoch cleared (before a bulk
+// change of the decay parameters or of the write-back period); the caller
+// then restarts the phase at 0.  Epochs of unscored topics and of retained or
+// absent pairs are cleared too, their counters untouched (nothing pends there).
+__global__ __launch_bounds__(256) void k_materialize(DevState s) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t t = blockIdx.y;
+    if (p >= s.n_pairs) return;
+    const size_t fi = flag_index(p, t, s.n_topics);
+    const uint8_t fl = s.rflags[fi];
+    const uint32_t k = rec_pend(s, s.pflags[p], fl, s.tp[t]);
+    if (k) rec_store_decayed(s, p, t, k);
+    if (fl & REC_EPOCH) s.rflags[fi] = fl & ~REC_EPOCH;
+}
+hipError_t launch_materialize(const DevState& s, hipStream_t st) {
+    if (s.n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_materialize, dim3(blocks_for(s.n_pairs, 256), s.n_topics), dim3(256), 0, st, s);
     return hipGetLastError();
 }
 

@@ -80,17 +80,102 @@ __device__ __forceinline__ int64_t mesh_time_of(const DevState& s, uint8_t fl, u
     return s.last_refresh - graft;
 }
 
+// x *= decay; x = 0 if x < DecayToZero   (score.go:527-542, 553-556)
+__device__ __forceinline__ double decay(double x, double d, double dtz) {
+    x *= d;
+    return x < dtz ? 0.0 : x;
+}
+
+// Every store to a record's MFP / IMD of a value that may be non-zero goes with
+// this mark (the zero map's invariant, gsx_device.h).  A plain byte store of
+// the constant: lanes racing on one tile's byte all write the same value.
+__device__ __forceinline__ void zmap_mark(const DevState& s, uint64_t p, uint32_t t, int field) {
+    s.zmap[zmap_index(p, t, s.n_topics, field)] = ZM_MAYBE;
+}
+
+// ---- deferred write-back of the decayed counters (REC_EPOCH, gsx_device.h) ----
+// The refresh pass stores the decayed counters only every wb_period-th
+// refresh; in between, a record's stored counters lag by rec_pend() decays.
+// decay() applied k times to the stored value is, bit for bit, what k
+// refreshes with a store after each would have left.  Outside the refresh pass
+// every access to a counter goes through rec_read (a reader) or
+// rec_materialize (before any read-modify-write).
+struct RecVals {
+    double fmd, mmd, mfp, imd;
+};
+
+// decays the stored counters of record (pair flags st, record flags fl) lag by
+__device__ __forceinline__ uint32_t rec_pend(const DevState& s, uint8_t st, uint8_t fl, const DevTopicParams& tp) {
+    return ((st & PAIR_CONNECTED) && tp.scored) ? ((s.phase - ((uint32_t)fl >> REC_EPOCH_SHIFT)) & 3u) : 0u;
+}
+
+__device__ __forceinline__ void rec_decay(RecVals& v, const DevTopicParams& tp, double dtz, uint32_t k) {
+    for (uint32_t i = 0; i < k; ++i) {
+        v.fmd = decay(v.fmd, tp.d2, dtz);
+        v.mmd = decay(v.mmd, tp.d3, dtz);
+        v.mfp = decay(v.mfp, tp.d3b, dtz);
+        v.imd = decay(v.imd, tp.d4, dtz);
+    }
+}
+
+// The record's counters as of the last refresh; stores nothing.
+__device__ __forceinline__ RecVals rec_read(const DevState& s, uint64_t p, uint32_t t, uint8_t st, uint8_t fl) {
+    const size_t b = rec_index(p, t, s.n_topics, FMD);
+    RecVals v = {s.rec[b + FMD * TILE], s.rec[b + MMD * TILE], s.rec[b + MFP * TILE], s.rec[b + IMD * TILE]};
+    rec_decay(v, s.tp[t], s.decay_to_zero, rec_pend(s, st, fl, s.tp[t]));
+    return v;
+}
+__device__ __forceinline__ RecVals rec_read(const DevState& s, uint64_t p, uint32_t t) {
+    return rec_read(s, p, t, s.pflags[p], s.rflags[flag_index(p, t, s.n_topics)]);
+}
+
+// k decays applied to the stored counters of a record, the changed ones stored.
+__device__ __forceinline__ void rec_store_decayed(const DevState& s, uint64_t p, uint32_t t, uint32_t k) {
+    const size_t b = rec_index(p, t, s.n_topics, FMD);
+    const RecVals o = {s.rec[b + FMD * TILE], s.rec[b + MMD * TILE], s.rec[b + MFP * TILE], s.rec[b + IMD * TILE]};
+    RecVals v = o;
+    rec_decay(v, s.tp[t], s.decay_to_zero, k);
+    if (__double_as_longlong(v.fmd) != __double_as_longlong(o.fmd)) s.rec[b + FMD * TILE] = v.fmd;
+    if (__double_as_longlong(v.mmd) != __double_as_longlong(o.mmd)) s.rec[b + MMD * TILE] = v.mmd;
+    if (__double_as_longlong(v.mfp) != __double_as_longlong(o.mfp)) {
+        if (__double_as_longlong(v.mfp) != 0) zmap_mark(s, p, t, MFP);
+        s.rec[b + MFP * TILE] = v.mfp;
+    }
+    if (__double_as_longlong(v.imd) != __double_as_longlong(o.imd)) {
+        if (__double_as_longlong(v.imd) != 0) zmap_mark(s, p, t, IMD);
+        s.rec[b + IMD * TILE] = v.imd;
+    }
+}
+
+// Brings the stored record up to date: applies its pending decays to all four
+// counters, stores the ones that changed and sets its epoch to the current
+// phase (the epoch is per record, hence the whole record).  -> the flag byte
+// as stored.  st: the pair's flags as the decays were skipped under (a pair
+// being disconnected passes its old, connected flags).
+__device__ __forceinline__ uint8_t rec_materialize(const DevState& s, uint64_t p, uint32_t t, uint8_t st) {
+    const size_t fi = flag_index(p, t, s.n_topics);
+    const uint8_t fl = s.rflags[fi];
+    const uint32_t k = rec_pend(s, st, fl, s.tp[t]);
+    if (k) rec_store_decayed(s, p, t, k);
+    const uint8_t nf = (uint8_t)((fl & ~REC_EPOCH) | (s.phase << REC_EPOCH_SHIFT));
+    if (nf != fl) s.rflags[fi] = nf;
+    return nf;
+}
+__device__ __forceinline__ uint8_t rec_materialize(const DevState& s, uint64_t p, uint32_t t) {
+    return rec_materialize(s, p, t, s.pflags[p]);
+}
+
 // score(p) from the stored state, no refresh (RemovePeer, score.go:615).
 __device__ __forceinline__ double eval_pair(const DevState& s, const DevPeerParams& pp, uint64_t p) {
-    if (!(s.pflags[p] & PAIR_PRESENT)) return 0.0;
+    const uint8_t st = s.pflags[p];
+    if (!(st & PAIR_PRESENT)) return 0.0;
     double score = 0.0;
     for (uint32_t t = 0; t < s.n_topics; ++t) {
         const DevTopicParams& tp = s.tp[t];
         if (!tp.scored) continue;
         const uint8_t fl = s.rflags[flag_index(p, t, s.n_topics)];
-        const size_t b = rec_index(p, t, s.n_topics, FMD);
-        score += topic_score(tp, fl, mesh_time_of(s, fl, p, t), s.rec[b], s.rec[b + MMD * TILE],
-                             s.rec[b + MFP * TILE], s.rec[b + IMD * TILE]);
+        const RecVals v = rec_read(s, p, t, st, fl);
+        score += topic_score(tp, fl, mesh_time_of(s, fl, p, t), v.fmd, v.mmd, v.mfp, v.imd);
     }
     return score_tail(s, pp, p, score, s.bp[p]);
 }
@@ -132,12 +217,6 @@ __device__ __forceinline__ double add_ones_capped(double x, uint32_t k, double c
     return x > cap ? cap : x;
 }
 
-// x *= decay; x = 0 if x < DecayToZero   (score.go:527-542, 553-556)
-__device__ __forceinline__ double decay(double x, double d, double dtz) {
-    x *= d;
-    return x < dtz ? 0.0 : x;
-}
-
 // ---- tracer updates (score.go:588-974) -----------------------------------------
 
 __device__ __forceinline__ void ipcount_add(const DevState& s, uint64_t p, int delta) {
@@ -146,28 +225,28 @@ __device__ __forceinline__ void ipcount_add(const DevState& s, uint64_t p, int d
     if (g.y != IPG_NONE && g.y != g.x) s.ipcount[g.y & ~IPG_WL] += (uint32_t)delta;
 }
 
-// Every store to a record's MFP / IMD of a value that may be non-zero goes with
-// this mark (the zero map's invariant, gsx_device.h).  A plain byte store of
-// the constant: lanes racing on one tile's byte all write the same value.
-__device__ __forceinline__ void zmap_mark(const DevState& s, uint64_t p, uint32_t t, int field) {
-    s.zmap[zmap_index(p, t, s.n_topics, field)] = ZM_MAYBE;
-}
-
 __device__ __forceinline__ bool scored_topic(const DevState& s, uint64_t p, uint32_t topic) {
     return (s.pflags[p] & PAIR_PRESENT) && topic < s.n_topics && s.tp[topic].scored;
 }
 
 __device__ inline void ev_add_peer(const DevState& s, uint64_t p) {  // AddPeer :588-602
     const uint8_t st = s.pflags[p];
+    const uint8_t ep = (uint8_t)(s.phase << REC_EPOCH_SHIFT);  // the records are current as of this phase
     if (!(st & PAIR_PRESENT)) {  // new peerStats{topics: {}}
         for (uint32_t t = 0; t < s.n_topics; ++t) {
             const size_t b = rec_index(p, t, s.n_topics, FMD);
             for (int f = 0; f < NFIELD; ++f) s.rec[b + f * TILE] = 0.0;
-            s.rflags[flag_index(p, t, s.n_topics)] = 0;
+            s.rflags[flag_index(p, t, s.n_topics)] = ep;
         }
         s.bp[p] = 0.0;
         s.expire[p] = 0;
         ipcount_add(s, p, +1);  // setIPs
+    } else if (!(st & PAIR_CONNECTED)) {  // a retained pair reconnects: it was not decayed meanwhile
+        for (uint32_t t = 0; t < s.n_topics; ++t) {
+            const size_t fi = flag_index(p, t, s.n_topics);
+            const uint8_t fl = s.rflags[fi];
+            if ((fl & REC_EPOCH) != ep) s.rflags[fi] = (uint8_t)((fl & ~REC_EPOCH) | ep);
+        }
     }
     s.pflags[p] = PAIR_PRESENT | PAIR_CONNECTED;
 }
@@ -180,13 +259,15 @@ __device__ inline void ev_remove_peer(const DevState& s, const DevPeerParams& pp
         s.pflags[p] = 0;
         return;
     }
+    // a retained pair is not decayed (and its epochs are not read) until it
+    // reconnects: every record is brought up to date now
     for (uint32_t t = 0; t < s.n_topics; ++t) {
         const DevTopicParams& tp = s.tp[t];
         if (!tp.scored) continue;
         const size_t b = rec_index(p, t, s.n_topics, FMD);
         const size_t fi = flag_index(p, t, s.n_topics);
+        const uint8_t fl = rec_materialize(s, p, t, st);
         s.rec[b + FMD * TILE] = 0.0;
-        const uint8_t fl = s.rflags[fi];
         const double threshold = tp.thr3;
         const double mmd = s.rec[b + MMD * TILE];
         if ((fl & REC_IN_MESH) && (fl & REC_ACTIVE) && mmd < threshold) {
@@ -203,14 +284,15 @@ __device__ inline void ev_remove_peer(const DevState& s, const DevPeerParams& pp
 __device__ inline void ev_graft(const DevState& s, uint64_t p, uint32_t topic, int64_t now) {  // :642-660
     if (!scored_topic(s, p, topic)) return;
     reinterpret_cast<int64_t*>(s.rec)[rec_index(p, topic, s.n_topics, GRAFT)] = now;
-    s.rflags[flag_index(p, topic, s.n_topics)] = REC_IN_MESH | REC_FRESH;  // meshTime = 0, not active
+    const size_t fi = flag_index(p, topic, s.n_topics);  // meshTime = 0, not active; the counters' epoch stays
+    s.rflags[fi] = (uint8_t)((s.rflags[fi] & REC_EPOCH) | REC_IN_MESH | REC_FRESH);
 }
 
 __device__ inline void ev_prune(const DevState& s, uint64_t p, uint32_t topic) {  // :662-684
     if (!scored_topic(s, p, topic)) return;
     const size_t b = rec_index(p, topic, s.n_topics, FMD);
     const size_t fi = flag_index(p, topic, s.n_topics);
-    const uint8_t fl = s.rflags[fi];
+    const uint8_t fl = rec_materialize(s, p, topic);
     const double threshold = s.tp[topic].thr3;
     const double mmd = s.rec[b + MMD * TILE];
     if ((fl & REC_ACTIVE) && mmd < threshold) {
@@ -225,10 +307,11 @@ __device__ inline void ev_first(const DevState& s, uint64_t p, uint32_t topic) {
     if (!scored_topic(s, p, topic)) return;
     const DevTopicParams& tp = s.tp[topic];
     const size_t b = rec_index(p, topic, s.n_topics, FMD);
+    const uint8_t fl = rec_materialize(s, p, topic);
     double f = s.rec[b + FMD * TILE] + 1;
     if (f > tp.cap2) f = tp.cap2;
     s.rec[b + FMD * TILE] = f;
-    if (!(s.rflags[flag_index(p, topic, s.n_topics)] & REC_IN_MESH)) return;
+    if (!(fl & REC_IN_MESH)) return;
     double m = s.rec[b + MMD * TILE] + 1;
     if (m > tp.cap3) m = tp.cap3;
     s.rec[b + MMD * TILE] = m;
@@ -237,6 +320,7 @@ __device__ inline void ev_first(const DevState& s, uint64_t p, uint32_t topic) {
 __device__ inline void ev_mesh(const DevState& s, uint64_t p, uint32_t topic) {  // :944-974 (window checked by caller)
     if (!scored_topic(s, p, topic)) return;
     if (!(s.rflags[flag_index(p, topic, s.n_topics)] & REC_IN_MESH)) return;
+    rec_materialize(s, p, topic);
     const size_t b = rec_index(p, topic, s.n_topics, MMD);
     double m = s.rec[b] + 1;
     if (m > s.tp[topic].cap3) m = s.tp[topic].cap3;
@@ -246,6 +330,7 @@ __device__ inline void ev_mesh(const DevState& s, uint64_t p, uint32_t topic) { 
 __device__ inline void ev_invalid(const DevState& s, uint64_t p, uint32_t topic) {  // :894-907
     if (!scored_topic(s, p, topic)) return;
     const size_t b = rec_index(p, topic, s.n_topics, IMD);
+    rec_materialize(s, p, topic);
     zmap_mark(s, p, topic, IMD);
     s.rec[b] = s.rec[b] + 1;
 }

@@ -1770,6 +1770,8 @@ __device__ __forceinline__ void fold_pair(const PropState& ps, const DevState& s
                                           uint32_t k4 = 0) {
     const DevTopicParams& tp = s.tp[ps.topic];
     const size_t b = rec_index(q, ps.topic, s.n_topics, FMD);
+    if ((k1 | k2 | k4) == 0) return;
+    const uint8_t fl = rec_materialize(s, q, ps.topic);
     // markInvalidMessageDelivery (score.go:894-907): k4 steps of +1, no cap
     if (k4) {
         zmap_mark(s, q, ps.topic, IMD);
@@ -1777,7 +1779,7 @@ __device__ __forceinline__ void fold_pair(const PropState& ps, const DevState& s
     }
     if (k1 == 0 && k2 == 0) return;
     s.rec[b + FMD * TILE] = add_ones_capped(s.rec[b + FMD * TILE], k1, tp.cap2);
-    if (!(s.rflags[flag_index(q, ps.topic, s.n_topics)] & REC_IN_MESH)) return;
+    if (!(fl & REC_IN_MESH)) return;
     s.rec[b + MMD * TILE] = add_ones_capped(s.rec[b + MMD * TILE], k1 + k2, tp.cap3);
 }
 
@@ -1805,9 +1807,8 @@ __device__ __forceinline__ double eval_pair_cached(const PropState& ps, const De
             double term;
             if (t == ps.topic) {
                 const uint8_t fl = s.rflags[flag_index(q, t, T)];
-                const size_t b = rec_index(q, t, T, FMD);
-                term = topic_score(tp, fl, mesh_time_of(s, fl, q, t), s.rec[b], s.rec[b + MMD * TILE],
-                                   s.rec[b + MFP * TILE], s.rec[b + IMD * TILE]);
+                const RecVals v = rec_read(s, q, t, s.pflags[q], fl);
+                term = topic_score(tp, fl, mesh_time_of(s, fl, q, t), v.fmd, v.mmd, v.mfp, v.imd);
                 tt[t] = term;
             } else {
                 term = tt[t];
@@ -1819,9 +1820,8 @@ __device__ __forceinline__ double eval_pair_cached(const PropState& ps, const De
             const DevTopicParams& tp = s.tp[t];
             if (!tp.scored) continue;
             const uint8_t fl = s.rflags[flag_index(q, t, T)];
-            const size_t b = rec_index(q, t, T, FMD);
-            const double term = topic_score(tp, fl, mesh_time_of(s, fl, q, t), s.rec[b], s.rec[b + MMD * TILE],
-                                            s.rec[b + MFP * TILE], s.rec[b + IMD * TILE]);
+            const RecVals v = rec_read(s, q, t, s.pflags[q], fl);
+            const double term = topic_score(tp, fl, mesh_time_of(s, fl, q, t), v.fmd, v.mmd, v.mfp, v.imd);
             tt[t] = term;
             score += term;
         }
@@ -1884,7 +1884,7 @@ __device__ __forceinline__ void fold_rescore_1(const PropState& ps, const DevSta
             ps.stale[q] = 1;
             if (!(fa[i] | da[i])) continue;
             const size_t b = rec_index(q, t, 1, FMD);
-            const uint8_t fl = s.rflags[flag_index(q, t, 1)];
+            const uint8_t fl = rec_materialize(s, q, t);
             s.rec[b + FMD * TILE] = add_ones_capped(s.rec[b + FMD * TILE], fa[i], s.tp[t].cap2);
             if (fl & REC_IN_MESH) s.rec[b + MMD * TILE] = add_ones_capped(s.rec[b + MMD * TILE], fa[i] + da[i], s.tp[t].cap3);
         }
@@ -1900,7 +1900,7 @@ __device__ __forceinline__ void fold_rescore_1(const PropState& ps, const DevSta
         if (!doit[i]) continue;
         const uint64_t q = q0 + i * stride;
         const size_t b = rec_index(q, t, 1, FMD);
-        fl[j] = s.rflags[flag_index(q, t, 1)];
+        fl[j] = rec_materialize(s, q, t);  // (the record is folded into below)
         fmd[j] = s.rec[b + FMD * TILE];
         mmd[j] = s.rec[b + MMD * TILE];
         mfp[j] = s.rec[b + MFP * TILE];

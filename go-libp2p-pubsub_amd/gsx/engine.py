@@ -863,6 +863,10 @@ class Engine:
         self._chk(self.lib.gsx_zero_map_violations(self.h, C.byref(n)), "gsx_zero_map_violations")
         return n.value
 
+    def set_decay_writeback(self, k: int) -> None:
+        """gsx_set_decay_writeback: the refresh pass stores the decayed counters every k-th refresh (1, 2, 4)."""
+        self._chk(self.lib.gsx_set_decay_writeback(self.h, k), "gsx_set_decay_writeback")
+
     def zero_map_marked(self) -> int:
         """gsx_zero_map_marked: zero-map entries (tile, topic, counter) that say "maybe non-zero"."""
         n = C.c_uint64()

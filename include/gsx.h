@@ -336,6 +336,14 @@ int gsx_zero_map_violations(gsx_engine* e, uint64_t* n);
  * a store of a non-zero penalty counter marks its tile's entry, a refresh that
  * finds the whole tile back at +0.0 clears it. */
 int gsx_zero_map_marked(gsx_engine* e, uint64_t* n);
+/* How often gsx_refresh stores the decayed counters: every k-th refresh, k in
+ * {1, 2, 4} (default 4).  A refresh's scores need the decayed values only in
+ * registers; in between, a record's stored counters lag by up to k - 1 decays,
+ * which every reader applies on the fly and every writer (events, credits,
+ * heartbeats) settles for its record first, so no result changes: scores,
+ * gsx_export_state and every other output are bit-identical for every k.
+ * k = 1 stores at every refresh.  Settles every record before switching. */
+int gsx_set_decay_writeback(gsx_engine* e, uint32_t k);
 
 /* WithPeerScoreInspect's extended view (ExtendedPeerScoreInspectFn,
  * inspectScoresExtended score.go:463-493): a PeerScoreSnapshot per pair

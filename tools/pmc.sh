@@ -29,7 +29,9 @@ run() {  # run NAME SECONDS COUNTER CMD...
 want() { [ -z "${PMC_SECTIONS:-}" ] || [[ " $PMC_SECTIONS " == *" $1 "* ]]; }
 for C in FETCH_SIZE WRITE_SIZE; do
     want calib && run calib 120 $C ./tools/microbench/pmc_calib
-    want head && run head 300 $C python3 bench.py --steps 5 --warmup 1 --no-cpu --no-dropin --no-single-observer --prop-msgs 0 \
+    # 8 launches: two whole write-back cycles of the default period (gsx_set_decay_writeback), so the
+    # per-launch average weighs storing and non-storing refreshes as a long run does
+    want head && run head 300 $C python3 bench.py --steps 7 --warmup 1 --no-cpu --no-dropin --no-single-observer --prop-msgs 0 \
         --prop-peers 0 --hb-steps 0 --adv-peers 0
     want p1024 && run p1024 200 $C python3 tools/prop_profile.py --msgs 1024 --batches 3 --warmup 2
     want p64 && run p64 200 $C python3 tools/prop_profile.py --msgs 64 --batches 3 --warmup 2
