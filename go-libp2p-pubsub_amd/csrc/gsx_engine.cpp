@@ -411,6 +411,7 @@ struct gsx_engine {
         uint64_t* touch = nullptr;     // bit per node: marked by a sender (very sparse hops)
         uint64_t* vcnt = nullptr;      // per node: forwarded-set sizes (late duplicate accounting)
         uint64_t halo_cap = 0, hfrom_cap = 0;
+        uint32_t halo_words = 0;       // the W the halo's rows were last laid out for (stride W + 1)
         unsigned long long* dcount = nullptr;
         // gsx_prop_stats: the device side of results that go to host memory (the
         // histogram grown when m grows, the per-node arrays sized once)
@@ -2896,8 +2897,8 @@ int prop_begin(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_conf
         if (int rc = dalloc(e, &P.from, (size_t)P.words_cap * E)) return rc;
         P.from_words = (size_t)P.words_cap * E;
     }
-    if (e->n_recv) {  // compacted exchange: engine-owned halo of tagged rows (no clears: a row
-                      // is empty unless its tag is this call's and hop's)
+    if (e->n_recv) {  // compacted exchange: engine-owned halo of tagged rows (no clears between
+                      // calls of one W: a row is empty unless its tag is this call's and hop's)
         if (P.halo_cap < (uint64_t)(W + 1) * e->n_recv) {
             if (P.halo) (void)hipFree(P.halo);
             P.halo = nullptr;
@@ -2905,7 +2906,12 @@ int prop_begin(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_conf
             if (int rc = dalloc(e, &P.halo, (size_t)(W + 1) * e->n_recv)) return rc;
             HIPCHK(e, hipMemsetAsync(P.halo, 0, 8 * (size_t)(W + 1) * e->n_recv, e->stream));  // (tag 0: no call's)
             P.halo_cap = (uint64_t)(W + 1) * e->n_recv;
+        } else if (P.halo_words != W) {
+            // the rows' stride is W + 1: at another W the tag column falls on an earlier call's
+            // data words (message bitmaps, which can equal a tag), so the old layout is cleared
+            HIPCHK(e, hipMemsetAsync(P.halo, 0, 8 * P.halo_cap, e->stream));
         }
+        P.halo_words = W;
         P.halo_tag = (uint64_t)(++P.halo_calls) << 8;  // (hops < 256)
     }
     if (e->n_send) {  // the compacted pack's per-(block, rank) table
@@ -4391,12 +4397,13 @@ int hb_begin_state(gsx_engine* e, uint64_t tick, int64_t now, uint64_t seed, boo
     }
     // IHAVE slots: this round's are written under its tag (k_hb_gossip); every
     // other slot reads as empty, so nothing is cleared (but at the tag's wrap)
-    if (++e->ihave_round == 0) {
+    if (++e->ihave_round == 0) {  // (the byte tags restart with the round counter: cur8 is 1 again)
         HIPCHK(e, hipMemsetAsync(e->d_ihave_slot, 0, sizeof(gsx::IhaveSlot) * (size_t)e->T * e->E, e->stream));
+        HIPCHK(e, hipMemsetAsync(e->d_ihave_tag, 0, (size_t)e->T * e->E, e->stream));
         e->ihave_round = 1;
     }
     // the targets' byte tags cycle 1..IHAVE_TAG_MAX: a stale byte equal to this
-    // round's can only be 127 rounds old, so the array is cleared as the cycle restarts
+    // round's can only be 63 rounds old, so the array is cleared as the cycle restarts
     const uint32_t cur8 = (e->ihave_round - 1) % gsx::IHAVE_TAG_MAX + 1;
     if (cur8 == 1 && e->ihave_round > 1)
         HIPCHK(e, hipMemsetAsync(e->d_ihave_tag, 0, (size_t)e->T * e->E, e->stream));

@@ -91,6 +91,27 @@ def test_gossip_exchange_per_node_validation_time(gpu_ok, kw):
     assert sum(o["fwd_duplicates"] for o in g[1]) > 0
 
 
+@pytest.mark.parametrize("kw", [dict(), dict(max_ihave_length=5)], ids=["whole_lists", "trunc5_own_slots"])
+def test_gossip_exchange_across_ihave_tag_cycles(gpu_ok, kw):
+    """130 heartbeats on one engine: the IHAVE targets' byte tags cycle 1..63
+    (IHAVE_TAG_MAX), so the rounds cross the tag's wrap and the clear that goes
+    with it twice (rounds 64 and 127).  A tag left from 63 rounds earlier that
+    read as this round's would send an IHAVE nobody emitted.  trunc5: every
+    list is cut to MaxIHaveLength 5 per target, so the targets' own slots
+    (their tags among the cycling bytes) are in play at the wraps."""
+    kw = dict(T=1, n=60, d=4, msgs=8, hops=1, ticks=130, **kw)
+    g = gc.exchange_run(gsx.Engine(1), **kw)
+    w = gc.exchange_run(orc.Oracle(1), **kw)
+    _same(g, w)
+    outs, snaps = g[1], g[2]
+    for k in (62, 63, 64, 125, 126, 127, 129):  # IHAVEs went out before, at and after both wraps
+        assert outs[k]["ihave_msgs"] > 0 and outs[k]["iwant_msgs"] > 0, (k, outs[k])
+        il = np.asarray(snaps[k]["ihave_len"])
+        assert (il > 0).any(), k
+        if "max_ihave_length" in kw:
+            assert il.max() == 5 and (il == 5).sum() > 10, (k, int(il.max()))
+
+
 def test_sets_cached_with_exchange_off_refuse_a_split_window(gpu_ok):
     """A batch propagated with the gossip exchange off keeps no arrival hops
     (its per-node validation times are not built): once the exchange is on, a
