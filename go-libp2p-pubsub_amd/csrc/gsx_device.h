@@ -390,6 +390,35 @@ hipError_t launch_prop_hops_export(const PropState& ps, uint8_t* hop_mn, hipStre
 constexpr uint32_t PROP_STATS_HOPS = 65;  // GSX_MAX_HOPS + 1
 hipError_t launch_prop_stats(const PropState& ps, uint32_t* msg_hop_hist, uint32_t* node_received,
                              unsigned long long* node_hop_sum, hipStream_t st);
+// gsx_score_stats (gsx_score_stats.hip): the selected pairs per score bin
+// (bin(s) = the edges k with s >= edges[k]) for the engine, per observer row
+// and per peer, and the lowest selected score per row and per peer.  Any
+// output may be null.  The counters are added to (the caller zeroes them); the
+// minima are held as order-preserving u64 keys of the doubles during the
+// pass: launch_score_stats_fill presets +inf, launch_score_stats_unkey leaves
+// doubles.
+constexpr uint32_t SS_MAX_EDGES = 7, SS_MAX_BINS = SS_MAX_EDGES + 1;  // GSX_SS_MAX_EDGES
+constexpr uint32_t SS_PRESENT = 0, SS_CONNECTED = 1, SS_MESH = 2;     // GSX_SS_*
+struct ScoreStatsArgs {
+    const double* score;
+    const uint8_t* pflags;
+    const uint8_t* rflags;     // tiled record flags (SS_MESH)
+    const uint32_t* pair_obs;  // per pair: local observer index
+    const int32_t* col;        // per pair: the peer's global node id
+    uint64_t n_pairs;
+    uint32_t n_topics, select, topic, n_edges;
+    double edges[SS_MAX_EDGES];
+    unsigned long long* hist;      // [n_edges + 1]
+    uint32_t* obs_bins;            // [n_local][n_edges + 1]
+    unsigned long long* obs_min;   // [n_local] keys
+    uint32_t* peer_bins;           // [n_total][n_edges + 1]
+    unsigned long long* peer_min;  // [n_total] keys
+};
+hipError_t launch_score_stats_fill(unsigned long long* obs_min, uint64_t n_obs, unsigned long long* peer_min,
+                                   uint64_t n_peer, hipStream_t st);
+hipError_t launch_score_stats(const ScoreStatsArgs& a, hipStream_t st);
+hipError_t launch_score_stats_unkey(unsigned long long* obs_min, uint64_t n_obs, unsigned long long* peer_min,
+                                    uint64_t n_peer, hipStream_t st);
 // The call's arrival hops as the validation-code planes of its message set
 // (VcRef: [plane][node][word], n_planes <= 8; hist rows 1 .. n_rows - 1).
 hipError_t launch_prop_vcodes(const PropState& ps, uint64_t* vc, uint32_t n_planes, hipStream_t st);

@@ -419,6 +419,11 @@ struct gsx_engine {
         size_t st_hist_cap = 0;
         uint32_t* st_recv = nullptr;
         unsigned long long* st_sum = nullptr;
+        // gsx_score_stats: the same for its five outputs, each sized once for
+        // GSX_SS_MAX_EDGES + 1 bins (per node, never per pair)
+        unsigned long long* ss_hist = nullptr;
+        uint32_t *ss_obs_bins = nullptr, *ss_peer_bins = nullptr;
+        unsigned long long *ss_obs_min = nullptr, *ss_peer_min = nullptr;
     } prop;
     bool prop_track = true;  // gsx_prop_set_tracking: keep first-deliverer rows (gsx_prop_results)
 
@@ -918,7 +923,8 @@ void free_state(gsx_engine* e) {
                   e->d_halo_pair, e->d_send_slot, e->d_rmark_v, e->d_rmark_u, e->prop.front_g, e->prop.occ_g,
                   e->prop.src_bits, e->prop.src_ids, e->prop.src_rows,
                   e->prop.d_dig, e->prop.rcand, e->prop.tterm, e->prop.tgen, e->prop.hist_alt, e->prop.occ_alt,
-                  e->prop.st_hist, e->prop.st_recv, e->prop.st_sum};
+                  e->prop.st_hist, e->prop.st_recv, e->prop.st_sum,
+                  e->prop.ss_hist, e->prop.ss_obs_bins, e->prop.ss_peer_bins, e->prop.ss_obs_min, e->prop.ss_peer_min};
     for (void* p : pp)
         if (p) (void)hipFree(p);
     std::vector<hipEvent_t> evs = std::move(e->prop.ev);
@@ -3912,6 +3918,97 @@ int gsx_prop_stats(gsx_engine* e, uint32_t* msg_hop_hist, uint32_t* node_receive
         host = true;
     }
     if (host) HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GSX_OK;
+}
+
+int gsx_score_stats_edges(gsx_engine* e, gsx_score_stats_spec* spec) {
+    if (!e || !spec) return GSX_EINVAL;
+    double v[6] = {e->th.graylist_threshold, e->th.publish_threshold,   e->th.gossip_threshold,
+                   0.0,                      e->th.accept_px_threshold, e->th.opportunistic_graft_threshold};
+    uint32_t n = 0;
+    for (double x : v)
+        if (!invalid_number(x)) v[n++] = x == 0.0 ? 0.0 : x;  // (-0.0 is the zero edge)
+    std::sort(v, v + n);
+    n = (uint32_t)(std::unique(v, v + n) - v);
+    static_assert(6 <= GSX_SS_MAX_EDGES, "the default edges fit");
+    spec->n_edges = n;
+    for (uint32_t k = 0; k < GSX_SS_MAX_EDGES; ++k) spec->edges[k] = k < n ? v[k] : 0.0;
+    return GSX_OK;
+}
+
+int gsx_score_stats(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_score_stats_out* out) {
+    static_assert(gsx::SS_MAX_EDGES == GSX_SS_MAX_EDGES && gsx::SS_PRESENT == GSX_SS_PRESENT &&
+                      gsx::SS_CONNECTED == GSX_SS_CONNECTED && gsx::SS_MESH == GSX_SS_MESH,
+                  "the kernel's constants are the header's");
+    if (!e || !spec || !out) return GSX_EINVAL;
+    if (spec->select > GSX_SS_MESH) return fail(e, GSX_EINVAL, "unknown selection");
+    if (spec->n_edges > GSX_SS_MAX_EDGES) return fail(e, GSX_EINVAL, "more than GSX_SS_MAX_EDGES edges");
+    for (uint32_t k = 0; k < spec->n_edges; ++k)
+        if (invalid_number(spec->edges[k]) || (k && !(spec->edges[k] > spec->edges[k - 1])))
+            return fail(e, GSX_EINVAL, "edges must be finite and strictly ascending");
+    if (spec->select == GSX_SS_MESH && spec->topic >= e->T) return fail(e, GSX_EINVAL, "topic out of range");
+    if (int rc = gx_busy(e)) return rc;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    if (!out->hist && !out->obs_bins && !out->obs_min && !out->peer_bins && !out->peer_min) return GSX_OK;
+    if (e->n_nodes == 0) return GSX_OK;
+    if (int rc = ensure_scores(e)) return rc;
+    auto& P = e->prop;
+    const size_t nb = (size_t)spec->n_edges + 1, NL = e->n_nodes, NT = e->n_total;
+    // device memory is written in place, in stream order; host memory gets a copy of the engine's buffers
+    const bool h_hist = out->hist && !on_device(out->hist), h_ob = out->obs_bins && !on_device(out->obs_bins),
+               h_om = out->obs_min && !on_device(out->obs_min), h_pb = out->peer_bins && !on_device(out->peer_bins),
+               h_pm = out->peer_min && !on_device(out->peer_min);
+    if (h_hist && !P.ss_hist)
+        if (int rc = dalloc(e, &P.ss_hist, gsx::SS_MAX_BINS)) return rc;
+    if (h_ob && !P.ss_obs_bins)
+        if (int rc = dalloc(e, &P.ss_obs_bins, NL * gsx::SS_MAX_BINS)) return rc;
+    if (h_om && !P.ss_obs_min)
+        if (int rc = dalloc(e, &P.ss_obs_min, NL)) return rc;
+    if (h_pb && !P.ss_peer_bins)
+        if (int rc = dalloc(e, &P.ss_peer_bins, NT * gsx::SS_MAX_BINS)) return rc;
+    if (h_pm && !P.ss_peer_min)
+        if (int rc = dalloc(e, &P.ss_peer_min, NT)) return rc;
+    using u64p = unsigned long long*;
+    const u64p d_hist = h_hist ? P.ss_hist : reinterpret_cast<u64p>(out->hist);
+    uint32_t* const d_ob = h_ob ? P.ss_obs_bins : out->obs_bins;
+    const u64p d_om = h_om ? P.ss_obs_min : reinterpret_cast<u64p>(out->obs_min);
+    uint32_t* const d_pb = h_pb ? P.ss_peer_bins : out->peer_bins;
+    const u64p d_pm = h_pm ? P.ss_peer_min : reinterpret_cast<u64p>(out->peer_min);
+    gsx::ScoreStatsArgs a{};
+    a.score = e->d_score;
+    a.pflags = e->d_pflags;
+    a.rflags = e->d_rflags;
+    a.pair_obs = e->d_pair_obs;
+    a.col = e->d_col;
+    a.n_pairs = e->E;
+    a.n_topics = e->T;
+    a.select = spec->select;
+    a.topic = spec->select == GSX_SS_MESH ? spec->topic : 0;
+    a.n_edges = spec->n_edges;
+    for (uint32_t k = 0; k < spec->n_edges; ++k) a.edges[k] = spec->edges[k];
+    a.hist = d_hist;
+    a.obs_bins = d_ob;
+    a.obs_min = d_om;
+    a.peer_bins = d_pb;
+    a.peer_min = d_pm;
+    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
+    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    if (d_hist) HIPCHK(e, hipMemsetAsync(d_hist, 0, 8 * nb, e->stream));
+    if (d_ob) HIPCHK(e, hipMemsetAsync(d_ob, 0, 4 * NL * nb, e->stream));
+    if (d_pb) HIPCHK(e, hipMemsetAsync(d_pb, 0, 4 * NT * nb, e->stream));
+    HIPCHK(e, gsx::launch_score_stats_fill(d_om, NL, d_pm, NT, e->stream));
+    HIPCHK(e, gsx::launch_score_stats(a, e->stream));
+    HIPCHK(e, gsx::launch_score_stats_unkey(d_om, NL, d_pm, NT, e->stream));
+    if (region) {
+        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
+        ++e->t_used;
+    }
+    if (h_hist) HIPCHK(e, hipMemcpyAsync(out->hist, d_hist, 8 * nb, hipMemcpyDeviceToHost, e->stream));
+    if (h_ob) HIPCHK(e, hipMemcpyAsync(out->obs_bins, d_ob, 4 * NL * nb, hipMemcpyDeviceToHost, e->stream));
+    if (h_om) HIPCHK(e, hipMemcpyAsync(out->obs_min, d_om, 8 * NL, hipMemcpyDeviceToHost, e->stream));
+    if (h_pb) HIPCHK(e, hipMemcpyAsync(out->peer_bins, d_pb, 4 * NT * nb, hipMemcpyDeviceToHost, e->stream));
+    if (h_pm) HIPCHK(e, hipMemcpyAsync(out->peer_min, d_pm, 8 * NT, hipMemcpyDeviceToHost, e->stream));
+    if (h_hist || h_ob || h_om || h_pb || h_pm) HIPCHK(e, hipStreamSynchronize(e->stream));
     return GSX_OK;
 }
 

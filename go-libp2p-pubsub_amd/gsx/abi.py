@@ -357,6 +357,37 @@ class HeartbeatOut(C.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+GSX_SS_MAX_EDGES = 7
+GSX_SS_PRESENT = 0
+GSX_SS_CONNECTED = 1
+GSX_SS_MESH = 2
+SS_SELECT = {"present": GSX_SS_PRESENT, "connected": GSX_SS_CONNECTED, "mesh": GSX_SS_MESH}
+
+
+class ScoreStatsSpec(C.Structure):
+    """gsx_score_stats_spec"""
+
+    _fields_ = [
+        ("select", C.c_uint32),
+        ("topic", C.c_uint32),
+        ("n_edges", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("edges", C.c_double * GSX_SS_MAX_EDGES),
+    ]
+
+
+class ScoreStatsOut(C.Structure):
+    """gsx_score_stats_out: host or device addresses, None skips an output"""
+
+    _fields_ = [
+        ("hist", C.c_void_p),
+        ("obs_bins", C.c_void_p),
+        ("obs_min", C.c_void_p),
+        ("peer_bins", C.c_void_p),
+        ("peer_min", C.c_void_p),
+    ]
+
+
 P = C.POINTER
 _u64p = P(C.c_uint64)
 
@@ -426,6 +457,8 @@ SIGNATURES = {
     "gsx_prop_results": (C.c_int, [C.c_void_p, P(C.c_uint8), P(C.c_int32)]),
     # (host or device pointers, like gsx_prop_pending_credits: passed as addresses)
     "gsx_prop_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsx_score_stats_edges": (C.c_int, [C.c_void_p, P(ScoreStatsSpec)]),
+    "gsx_score_stats": (C.c_int, [C.c_void_p, P(ScoreStatsSpec), P(ScoreStatsOut)]),
     "gsx_prop_set_tracking": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_prop_duplicates": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_size_t]),
     "gsx_set_pair_ips": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint32), C.c_size_t]),

@@ -118,6 +118,75 @@ class PropStats:
                          sum(p.node_hop_sum for p in parts) if per_node else None)
 
 
+class ScoreStats:
+    """Threshold standings of the scores (gsx_score_stats): the selected pairs
+    per score bin, bin(s) = the edges k with s >= edges[k], as hist [B] u64 for
+    the engine, obs_bins [n_local, B] u32 per observer row with obs_min
+    [n_local] f64 (the row's lowest selected score, +inf if none), peer_bins
+    [n_total, B] u32 per peer with peer_min [n_total] f64; B = len(edges) + 1.
+    Any of them may be None.  Everything below is numpy on those tables."""
+
+    def __init__(self, edges, hist=None, obs_bins=None, obs_min=None, peer_bins=None, peer_min=None):
+        self.edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        B = len(self.edges) + 1
+        self.hist = None if hist is None else np.ascontiguousarray(hist, dtype=np.uint64).reshape(B)
+        self.obs_bins = None if obs_bins is None else np.ascontiguousarray(obs_bins, dtype=np.uint32).reshape(-1, B)
+        self.obs_min = None if obs_min is None else np.ascontiguousarray(obs_min, dtype=np.float64).reshape(-1)
+        self.peer_bins = None if peer_bins is None else np.ascontiguousarray(peer_bins, dtype=np.uint32).reshape(-1, B)
+        self.peer_min = None if peer_min is None else np.ascontiguousarray(peer_min, dtype=np.float64).reshape(-1)
+
+    def _edge(self, x) -> int:
+        k = np.nonzero(self.edges == x)[0]
+        if len(k) == 0:
+            raise ValueError(f"{x} is not one of the edges {self.edges.tolist()}")
+        return int(k[0])
+
+    def below(self, x):
+        """The selected pairs with score < x, x one of the edges -> (hist: int, obs [n_local] i64,
+        peer [n_total] i64); None for a table the call did not ask for."""
+        k = self._edge(x) + 1
+        return (None if self.hist is None else int(self.hist[:k].sum()),
+                None if self.obs_bins is None else self.obs_bins[:, :k].sum(1, dtype=np.int64),
+                None if self.peer_bins is None else self.peer_bins[:, :k].sum(1, dtype=np.int64))
+
+    def degree(self) -> np.ndarray:
+        """[n_local] i64: the selected pairs of each row (select="mesh", any edges: the mesh degree)."""
+        return self.obs_bins.sum(1, dtype=np.int64)
+
+    def indegree(self) -> np.ndarray:
+        """[n_total] i64: the selected pairs that point at each node."""
+        return self.peer_bins.sum(1, dtype=np.int64)
+
+    def fraction_below(self, x):
+        """below(x) over the totals -> (hist: float, obs [n_local] f64, peer [n_total] f64); nan where
+        nothing is selected."""
+        h, o, p = self.below(x)
+
+        def frac(a, tot):
+            tot = np.asarray(tot, dtype=np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return np.where(tot > 0, np.asarray(a, dtype=np.float64) / np.maximum(tot, 1), np.nan)
+
+        return (None if h is None else float(frac(h, int(self.hist.sum()))),
+                None if o is None else frac(o, self.degree()),
+                None if p is None else frac(p, self.indegree()))
+
+    def __add__(self, other: "ScoreStats") -> "ScoreStats":
+        """Range shards' local tables, in rank order: hist and the peer counters add up, peer_min
+        takes the lower, the observer arrays follow one another (kept when both sides have them)."""
+        if not np.array_equal(self.edges, other.edges):
+            raise ValueError("tables over different edges")
+
+        def both(a, b, f):
+            return None if a is None or b is None else f(a, b)
+
+        return ScoreStats(self.edges, both(self.hist, other.hist, np.add),
+                          both(self.obs_bins, other.obs_bins, lambda a, b: np.concatenate([a, b], 0)),
+                          both(self.obs_min, other.obs_min, lambda a, b: np.concatenate([a, b])),
+                          both(self.peer_bins, other.peer_bins, np.add),
+                          both(self.peer_min, other.peer_min, np.minimum))
+
+
 class Engine:
     def __init__(self, n_topics: int, device: int = 0):
         self.lib = abi.load_library()
@@ -180,6 +249,8 @@ class Engine:
         self._chk(self.lib.gsx_num_pairs(self.h, C.byref(v)), "gsx_num_pairs")
         self.n_pairs = int(v.value)
         self.n_nodes = n
+        self.node_lo = 0
+        self.n_total = n
 
     def set_ip_whitelist(self, ips: Iterable[int]):
         a = np.ascontiguousarray(list(ips), dtype=np.uint32)
@@ -481,6 +552,45 @@ class Engine:
                                           C.c_void_p(hsum.ctypes.data if per_node and hsum.size else None)),
                   "gsx_prop_stats")
         return PropStats(hist, recv, hsum)
+
+    def score_stats_edges(self) -> np.ndarray:
+        """gsx_score_stats_edges: the sorted, de-duplicated thresholds of the last set_thresholds and 0.0."""
+        sp = abi.ScoreStatsSpec()
+        self._chk(self.lib.gsx_score_stats_edges(self.h, C.byref(sp)), "gsx_score_stats_edges")
+        return np.array(sp.edges[: sp.n_edges], dtype=np.float64)
+
+    def score_stats(self, edges=None, select="present", topic: int = 0, per_node: bool = True, peers: bool = True,
+                    out_ptrs=None):
+        """gsx_score_stats -> ScoreStats: the selected pairs (select: "present", "connected" or
+        "mesh" on `topic`) per score bin over `edges` (None: score_stats_edges()), for the engine,
+        with per_node per observer row (and the row's lowest score), with peers per peer.
+
+        out_ptrs = (hist, obs_bins, obs_min, peer_bins, peer_min): device pointers or tensors
+        (None / 0 skips one) written in stream order with no host sync, as prop_stats takes
+        them; then -> None."""
+        sp = abi.ScoreStatsSpec(select=abi.SS_SELECT[select] if isinstance(select, str) else int(select),
+                                topic=int(topic))
+        if edges is None:
+            self._chk(self.lib.gsx_score_stats_edges(self.h, C.byref(sp)), "gsx_score_stats_edges")
+        else:
+            ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+            sp.n_edges = len(ed)
+            for k, x in enumerate(ed[: abi.GSX_SS_MAX_EDGES]):
+                sp.edges[k] = x
+        if out_ptrs is not None:
+            out = abi.ScoreStatsOut(*[self._p(p).value if p is not None else None for p in out_ptrs])
+            self._chk(self.lib.gsx_score_stats(self.h, C.byref(sp), C.byref(out)), "gsx_score_stats")
+            return None
+        B = min(sp.n_edges, abi.GSX_SS_MAX_EDGES) + 1
+        nl, nt = self.n_nodes, getattr(self, "n_total", self.n_nodes)
+        hist = np.zeros(B, dtype=np.uint64)
+        ob = np.zeros((nl, B), dtype=np.uint32) if per_node else None
+        om = np.full(nl, np.inf) if per_node else None
+        pb = np.zeros((nt, B), dtype=np.uint32) if peers else None
+        pm = np.full(nt, np.inf) if peers else None
+        out = abi.ScoreStatsOut(*[a.ctypes.data if a is not None and a.size else None for a in (hist, ob, om, pb, pm)])
+        self._chk(self.lib.gsx_score_stats(self.h, C.byref(sp), C.byref(out)), "gsx_score_stats")
+        return ScoreStats(np.array(sp.edges[: B - 1], dtype=np.float64), hist, ob, om, pb, pm)
 
     def pending_credits(self, first_ptr: int, dup_ptr: int):
         """Copy the pending (GSX_CREDIT_DEFER) counts to caller memory (host or device pointers)."""

@@ -308,6 +308,40 @@ class RangeSharded:
                              recv.cpu().numpy().view(np.uint32) if per_node else None,
                              hsum.cpu().numpy().view(np.uint64) if per_node else None)
 
+    def score_stats(self, edges=None, select="present", topic: int = 0, per_node: bool = True, peers: bool = True):
+        """gsx_score_stats over the whole overlay -> ScoreStats: every rank writes its pairs' tables
+        into device tensors (no host sync); one all-reduce sums hist and peer_bins (as int64:
+        torch reduces no unsigned 32-bit integers), peer_min is reduced as -max(-x).  The observer
+        arrays are this rank's rows; they stay per rank."""
+        torch = _torch()
+        from .engine import ScoreStats
+
+        be = self.be
+        ed = be.score_stats_edges() if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        B = len(ed) + 1
+        with self._on_stream():
+            dev = self.tp.device
+            nl, nt = be.n_nodes, int(self.rank_lo[-1])
+            # (an engine of no nodes writes nothing: the tensors start as the sums' and the min's identities)
+            hist = torch.zeros(B, dtype=torch.int64, device=dev)
+            ob = torch.zeros((nl, B), dtype=torch.int32, device=dev) if per_node else None
+            om = torch.full((nl,), float("inf"), dtype=torch.float64, device=dev) if per_node else None
+            pb = torch.zeros((nt, B), dtype=torch.int32, device=dev) if peers else None
+            pm = torch.full((nt,), float("inf"), dtype=torch.float64, device=dev) if peers else None
+            be.score_stats(ed, select, topic, out_ptrs=(hist, ob if nl else None, om if nl else None, pb, pm))
+            tot = torch.cat([hist, (pb.to(torch.int64) & 0xFFFFFFFF).reshape(-1)]) if peers else hist
+            self.tp.all_reduce_sum(tot)
+            if peers:
+                neg = -pm
+                self.tp.all_reduce_max(neg)
+                pm = -neg
+            t = tot.cpu().numpy()
+            return ScoreStats(ed, t[:B].view(np.uint64),
+                              ob.cpu().numpy().view(np.uint32) if per_node else None,
+                              om.cpu().numpy() if per_node else None,
+                              t[B:].reshape(nt, B).astype(np.uint32) if peers else None,
+                              pm.cpu().numpy() if peers else None)
+
 
     def _propagate_rep(self, W, cfg) -> int:
         """The replicated frontier (gsx.h gsx_prop_rep_*): the cross pairs' fwd

@@ -326,6 +326,62 @@ typedef struct gsx_state_view {
 int gsx_import_state(gsx_engine* e, const gsx_state_view* s);
 int gsx_export_state(gsx_engine* e, gsx_state_view* s);
 
+/* ---- threshold standings of the scores, reduced on the device --------------- */
+/* Everything the protocol does with a score is a comparison with a threshold
+ * (graylist, publish, gossip, zero, acceptPX, opportunistic graft).  This
+ * counts the selected pairs per score bin without the score vector leaving
+ * the device: for the engine, per observer row (how many of its peers a
+ * router graylists, its mesh degree) and per peer (how many observers
+ * graylist a node).
+ *
+ * bin(s) = the number of k with s >= edges[k], 0 .. n_edges: a score exactly
+ * on an edge falls in the upper bin (the reference's gates are all
+ * score < threshold).  With n_edges == 0 every selected pair is in bin 0:
+ * obs_bins[u] is then row u's selected pairs — under GSX_SS_MESH the node's
+ * mesh degree on spec.topic. */
+#define GSX_SS_MAX_EDGES 7
+#define GSX_SS_PRESENT 0u   /* every pair with a peerStats entry (GSX_PAIR_PRESENT)  */
+#define GSX_SS_CONNECTED 1u /* present and connected                                 */
+#define GSX_SS_MESH 2u      /* present, connected and GSX_REC_IN_MESH on spec.topic  */
+
+typedef struct gsx_score_stats_spec {
+    uint32_t select;  /* GSX_SS_*                     */
+    uint32_t topic;   /* GSX_SS_MESH only; < n_topics */
+    uint32_t n_edges; /* 0 .. GSX_SS_MAX_EDGES        */
+    uint32_t reserved;
+    double edges[GSX_SS_MAX_EDGES]; /* finite, strictly ascending */
+} gsx_score_stats_spec;
+
+/* n_local: this engine's nodes; n_total: the overlay's (the same on an
+ * unsharded engine; on a range shard col holds global ids, so the peer arrays
+ * cover every node of the overlay: the sum over ranks of peer_bins and the
+ * min over ranks of peer_min are the whole overlay's). */
+typedef struct gsx_score_stats_out { /* every pointer: NULL (skipped), host or device memory */
+    uint64_t* hist;      /* [n_edges + 1]           selected pairs per bin, this engine */
+    uint32_t* obs_bins;  /* [n_local][n_edges + 1]  row u: u's selected peers per bin   */
+    double* obs_min;     /* [n_local]               lowest selected score in row u; +inf if none */
+    uint32_t* peer_bins; /* [n_total][n_edges + 1]  node v: selected pairs p with col[p] == v, per bin */
+    double* peer_min;    /* [n_total]               lowest score any selected pair holds of v; +inf if none */
+} gsx_score_stats_out;
+
+/* Fills n_edges and edges with the sorted, de-duplicated finite values of
+ * {graylist, publish, gossip, 0.0, accept_px, opportunistic_graft} of the last
+ * gsx_set_thresholds (at most 6); leaves select and topic alone. */
+int gsx_score_stats_edges(gsx_engine* e, gsx_score_stats_spec* spec);
+/* Reads exactly what gsx_scores would return (the same settling of deferred
+ * folds, queued events and stale pairs first) and changes nothing a later
+ * call can observe.  Device outputs are written in stream order with no host
+ * synchronisation; host outputs are complete on return (through buffers the
+ * engine keeps; no temporary is of the size of the pair set).  All integer
+ * adds and mins: bit-identical from run to run.  Inside a gsx_timing_begin
+ * region the call's device work counts as one timed launch.
+ * GSX_EINVAL: a NULL argument, an unknown select, n_edges > GSX_SS_MAX_EDGES,
+ * edges not finite or not strictly ascending, topic >= n_topics under
+ * GSX_SS_MESH.  GSX_ESTATE: no overlay loaded, or a sharded gossip exchange in
+ * flight.  An engine of no nodes writes nothing; no selected pair leaves
+ * zeros and +inf; all outputs NULL returns at once. */
+int gsx_score_stats(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_score_stats_out* out);
+
 /* A consistency check of the engine's zero map (per 64-pair tile,
  * topic and penalty counter, "every present pair holds +0.0", which lets the
  * refresh pass skip the counter's load): *n = the entries that say zero while
