@@ -282,6 +282,9 @@ struct PropState {
     const uint64_t* fanout;             // [pair]: topics whose fanout holds the peer
     uint32_t gate;                      // gossipsub: receivers drop copies from graylisted senders (FWD_GIN)
     unsigned long long* gray_pairs;     // pairs with FWD_GIN (counted by k_prop_fwd, kept with fwd)
+    // gsx_gater_enforce: the decision bytes of the last full gsx_accept_from ([pair] GSX_ACCEPT_*;
+    // null: off).  AcceptControl (1) drops the sender's payload like AcceptNone does: FWD_GIN.
+    const uint8_t* gdec;
     int64_t hop_latency, window;
     uint64_t seed;
     uint32_t* hop_flag;  // host-mapped, [hop]: k_prop_mark(h) stores (hop_seq << 1) | (hop h-1 delivered); null: off
@@ -419,6 +422,71 @@ hipError_t launch_score_stats_fill(unsigned long long* obs_min, uint64_t n_obs, 
 hipError_t launch_score_stats(const ScoreStatsArgs& a, hipStream_t st);
 hipError_t launch_score_stats_unkey(unsigned long long* obs_min, uint64_t n_obs, unsigned long long* peer_min,
                                     uint64_t n_peer, hipStream_t st);
+// The peer gater (gsx_gater.hip; peer_gater.go).  Per observer: validate,
+// throttle, last_throttle and the `hot` byte of the last gsx_accept_from (quiet
+// period, throttle and ratio all say "gate on").  Per group g (an (observer, IP)
+// pair; gsx.h): connected, expire and the four counters as one 32-byte record
+// ctr[4 g + GC_*], so a hot lane gathers them in one aligned access.  Per pair:
+// the group it is bound to.
+constexpr uint32_t GATER_UNBOUND = 0xFFFFFFFFu;
+constexpr int64_t GATER_NEVER = INT64_MIN;
+constexpr int GC_DELIVER = 0, GC_DUPLICATE = 1, GC_IGNORE = 2, GC_REJECT = 3;
+constexpr uint64_t TAG_GATER = 14;  // draw tag of AcceptFrom's u (gsx.h)
+constexpr uint8_t ACCEPT_NONE = 0, ACCEPT_CONTROL = 1, ACCEPT_ALL = 2;  // GSX_ACCEPT_*
+struct GaterState {
+    double* validate;        // [n_obs]
+    double* throttle;        // [n_obs]
+    int64_t* last_throttle;  // [n_obs], GATER_NEVER
+    uint8_t* hot;            // [n_obs]
+    uint32_t* connected;     // [n_groups]
+    int64_t* expire;         // [n_groups]
+    double* ctr;             // [n_groups][4], 32-byte aligned
+    uint32_t* bind;          // [n_pairs]
+    uint32_t n_obs, n_groups;
+    uint64_t n_pairs;
+    double threshold, global_decay, source_decay, decay_to_zero;
+    double duplicate_weight, ignore_weight, reject_weight;
+    int64_t retain_ns, quiet_ns;
+};
+// Device kinds: the ABI's, with REJECT split by what the reason does.
+constexpr uint32_t GEV_ADD = 1, GEV_REMOVE = 2, GEV_VALIDATE = 3, GEV_DELIVER = 4, GEV_DUPLICATE = 5, GEV_THROTTLE = 6,
+                   GEV_IGNORE = 7, GEV_REJECT = 8;
+struct DevGaterEvent {  // sorted by observer, like DevEvent
+    uint32_t kind;
+    uint32_t group;  // GEV_ADD: the pair's group as the host resolved it at the call
+    uint64_t pair;
+    int64_t now_ns;
+    double weight;  // GEV_DELIVER: the topic's delivery weight (0 already mapped to 1)
+};
+hipError_t launch_gater_events(const GaterState& g, const uint32_t* pair_obs, const DevGaterEvent* ev,
+                               const uint32_t* group_off, uint32_t n_obs_groups, hipStream_t st);
+hipError_t launch_gater_decay(const GaterState& g, int64_t now, hipStream_t st);
+struct AcceptArgs {
+    const double* score;
+    const uint8_t* pflags;
+    const uint8_t* eflags;
+    const uint32_t* pair_obs;
+    const uint64_t* pairs;  // null: every pair, out[p]; else out[i] for pairs[i]
+    uint64_t n;
+    double graylist_threshold;
+    int64_t now;
+    uint64_t seed, draw;
+    uint32_t gater;  // 0: no gater, the third stage accepts
+    uint8_t* out;
+};
+// k_gater_hot over the observers, then k_accept_from.
+hipError_t launch_accept_from(const GaterState& g, const AcceptArgs& a, hipStream_t st);
+// gsx_gater_fold_prop: the per-group (gcnt [n_groups][4], GC_* order) and
+// per-observer (ocnt [n_obs][2]: first receipts, THROTTLE first receipts)
+// integer counts of the last propagation, from its first-deliverer rows, its
+// duplicate rows (k_prop_dup_rows' output) and the validation classes of its
+// messages (cls [4][W]: GSX_VALIDATION_* order); then their application, which
+// leaves the counts zero.
+hipError_t launch_gater_fold_count(const GaterState& g, const uint32_t* pair_obs, const uint64_t* from_mask,
+                                   const uint64_t* dup_rows, const uint64_t* cls, uint32_t n_words, uint32_t* gcnt,
+                                   uint32_t* ocnt, hipStream_t st);
+hipError_t launch_gater_fold_apply(const GaterState& g, uint32_t* gcnt, uint32_t* ocnt, double weight, int64_t now,
+                                   hipStream_t st);
 // The call's arrival hops as the validation-code planes of its message set
 // (VcRef: [plane][node][word], n_planes <= 8; hist rows 1 .. n_rows - 1).
 hipError_t launch_prop_vcodes(const PropState& ps, uint64_t* vc, uint32_t n_planes, hipStream_t st);

@@ -385,6 +385,7 @@ struct gsx_engine {
             bool valid = false;
             uint32_t router = 0, topic = 0, flood_publish = 0;
             uint64_t flag_gen = 0, score_gen = 0, mem_gen = 0;
+            uint64_t dec_gen = 0;  // gater_dec_gen under enforcement, else 0
             double publish_threshold = 0, graylist_threshold = 0;
         } fwd_key;
         bool fold_chg = false;  // the last call's fold listed fwd changes for the next call's pins
@@ -426,6 +427,36 @@ struct gsx_engine {
         unsigned long long *ss_obs_min = nullptr, *ss_peer_min = nullptr;
     } prop;
     bool prop_track = true;  // gsx_prop_set_tracking: keep first-deliverer rows (gsx_prop_results)
+
+    // the peer gater (gsx_set_gater_params; gsx_gater.hip): device arrays per
+    // observer, per gater group (n_nodes "<unknown>" groups, then the engine's
+    // (observer, IP) groups: grown with n_groups) and per pair
+    struct {
+        bool on = false;
+        gsx_gater_params p{};
+        double *validate = nullptr, *throttle = nullptr, *ctr = nullptr;
+        int64_t *last = nullptr, *expire = nullptr;
+        uint8_t* hot = nullptr;
+        uint32_t *connected = nullptr, *bind = nullptr;
+        uint32_t groups = 0;           // allocated gater groups (n_nodes + n_groups as of the last growth)
+        uint8_t* decision = nullptr;   // [pair] the last full gsx_accept_from
+        bool have_decision = false;
+        uint8_t* list_out = nullptr;   // a listed call's pairs and bytes (grown)
+        uint64_t* list_pairs = nullptr;
+        size_t list_cap = 0;
+        void* ev = nullptr;            // gsx_gater_events' device staging (grown)
+        size_t ev_bytes = 0;
+        uint32_t *gcnt = nullptr, *ocnt = nullptr;  // gsx_gater_fold_prop's counts (zero between calls)
+        uint32_t gcnt_groups = 0;
+        uint64_t* fold_buf = nullptr;  // gsx_gater_fold_prop: the duplicate rows [E][W], then the class masks [4][W] (grown)
+        size_t fold_cap = 0;
+        bool enforce = false;          // gsx_gater_enforce: gossipsub propagation reads `decision`
+        uint64_t n_none = 0, n_control = 0;  // gsx_gater_gate_pairs of the decision set (counted on demand)
+        bool counted = false;
+    } gater;
+    // bumped by every full gsx_accept_from and every gsx_gater_enforce: the fwd bytes of a
+    // propagation are reused only under the decision set they were computed from (never reset)
+    uint64_t gater_dec_gen = 0;
 
     // range sharding (gsx_load_overlay_shard / gsx_shard_*_plan)
     uint32_t n_total = 0, node_lo = 0;
@@ -874,6 +905,19 @@ void gx_abort(gsx_engine* e) {
     R.stage = 0;
 }
 
+// Frees the gater with everything that hangs on it (the decision set, enforcement);
+// no later fold may read the freed decision bytes through the last call's state.
+void gater_free(gsx_engine* e) {
+    auto& G = e->gater;
+    void* gp[] = {G.validate, G.throttle,   G.ctr,        G.last, G.expire, G.hot,  G.connected, G.bind,
+                  G.decision, G.list_out,   G.list_pairs, G.ev,   G.gcnt,   G.ocnt, G.fold_buf};
+    for (void* p : gp)
+        if (p) (void)hipFree(p);
+    G = {};
+    e->prop.last.gdec = nullptr;
+    ++e->gater_dec_gen;
+}
+
 void free_state(gsx_engine* e) {
     if (e->vc_stream) (void)hipStreamSynchronize(e->vc_stream);  // (code-plane builds in flight)
     e->vc_busy[0] = e->vc_busy[1] = false;
@@ -935,6 +979,7 @@ void free_state(gsx_engine* e) {
     e->prop.hop_flag = hf;
     e->prop.d_hop_flag = dhf;
     e->prop.hop_seq = hseq;
+    gater_free(e);  // the gater belongs to the overlay it was set on
     e->d_send_pair = e->d_pair_obs = e->d_halo_node = e->d_halo_pair = e->d_send_slot = nullptr;
     e->d_rmark_v = e->d_rmark_u = nullptr;
     e->d_send_dest = nullptr;
@@ -1058,6 +1103,85 @@ int dalloc(gsx_engine* e, T** p, size_t n) {
     hipError_t st = hipMalloc((void**)p, sizeof(T) * (n ? n : 1));
     if (st != hipSuccess) return fail(e, GSX_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(st));
     return GSX_OK;
+}
+
+// ---- the peer gater's state (gsx.h; kernels in gsx_gater.hip) ------------------
+gsx::GaterState dev_gater(const gsx_engine* e) {
+    const auto& G = e->gater;
+    gsx::GaterState g{};
+    g.validate = G.validate;
+    g.throttle = G.throttle;
+    g.last_throttle = G.last;
+    g.hot = G.hot;
+    g.connected = G.connected;
+    g.expire = G.expire;
+    g.ctr = G.ctr;
+    g.bind = G.bind;
+    g.n_obs = e->n_nodes;
+    g.n_groups = G.groups;
+    g.n_pairs = e->E;
+    g.threshold = G.p.threshold;
+    g.global_decay = G.p.global_decay;
+    g.source_decay = G.p.source_decay;
+    g.decay_to_zero = G.p.decay_to_zero;
+    g.duplicate_weight = G.p.duplicate_weight;
+    g.ignore_weight = G.p.ignore_weight;
+    g.reject_weight = G.p.reject_weight;
+    g.retain_ns = G.p.retain_stats_ns;
+    g.quiet_ns = G.p.quiet_ns;
+    return g;
+}
+
+// The group arrays cover n_nodes "<unknown>" groups and every (observer, IP)
+// group of the engine: longer arrays when gsx_set_pair_ips made new groups,
+// the old entries kept.
+int gater_grow(gsx_engine* e) {
+    auto& G = e->gater;
+    const uint32_t want = e->n_nodes + e->n_groups;
+    if (!G.on || want <= G.groups) return GSX_OK;
+    uint32_t* nc = nullptr;
+    int64_t* ne = nullptr;
+    double* nr = nullptr;
+    int rc = 0;
+    if ((rc = dalloc(e, &nc, want)) || (rc = dalloc(e, &ne, want)) || (rc = dalloc(e, &nr, 4 * (size_t)want))) {
+        if (nc) (void)hipFree(nc);
+        if (ne) (void)hipFree(ne);
+        return rc;
+    }
+    hipError_t st = hipMemsetAsync(nc, 0, 4 * (size_t)want, e->stream);
+    if (st == hipSuccess) st = hipMemsetAsync(ne, 0, 8 * (size_t)want, e->stream);
+    if (st == hipSuccess) st = hipMemsetAsync(nr, 0, 32 * (size_t)want, e->stream);
+    if (st == hipSuccess && G.groups) {
+        st = hipMemcpyAsync(nc, G.connected, 4 * (size_t)G.groups, hipMemcpyDeviceToDevice, e->stream);
+        if (st == hipSuccess) st = hipMemcpyAsync(ne, G.expire, 8 * (size_t)G.groups, hipMemcpyDeviceToDevice, e->stream);
+        if (st == hipSuccess) st = hipMemcpyAsync(nr, G.ctr, 32 * (size_t)G.groups, hipMemcpyDeviceToDevice, e->stream);
+    }
+    const hipError_t st2 = hipStreamSynchronize(e->stream);
+    if (st != hipSuccess || st2 != hipSuccess) {  // the old arrays stand
+        (void)hipFree(nc);
+        (void)hipFree(ne);
+        (void)hipFree(nr);
+        HIPCHK(e, st);
+        HIPCHK(e, st2);
+    }
+    if (G.connected) (void)hipFree(G.connected);
+    if (G.expire) (void)hipFree(G.expire);
+    if (G.ctr) (void)hipFree(G.ctr);
+    G.connected = nc;
+    G.expire = ne;
+    G.ctr = nr;
+    G.groups = want;
+    return GSX_OK;
+}
+
+// The gater group of a pair as its IP list stands: its first IP id's
+// (observer, IP) group, or its observer's "<unknown>" group.
+uint32_t gater_group_of(const gsx_engine* e, uint64_t pair) {
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t g = e->ipg_host[2 * (size_t)pair + k];
+        if (g != gsx::IPG_NONE) return e->n_nodes + g;
+    }
+    return e->pair_obs[pair];
 }
 
 // Staging buffer for one topic-major record field (import / export only).
@@ -1983,6 +2107,7 @@ int gsx_set_pair_ips(gsx_engine* e, const uint64_t* pairs, const uint32_t* ips, 
         HIPCHK(e, hipStreamSynchronize(e->stream));
         (void)hipFree(e->d_ipcount);
         e->d_ipcount = nc;
+        if (int rc = gater_grow(e)) return rc;  // the gater's group arrays follow n_groups
     }
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return obs[a] < obs[b]; });
     std::vector<gsx::DevIpMove> sorted(n);
@@ -2762,6 +2887,7 @@ gsx::PropState prop_state(gsx_engine* e, uint32_t W, size_t m, const gsx_prop_co
     ps.gate = cfg->router == GSX_ROUTER_GOSSIPSUB ? 1 : 0;
     ps.graylist_threshold = e->th.graylist_threshold;
     ps.gray_pairs = P.gray_pairs;
+    ps.gdec = (e->gater.enforce && ps.gate) ? e->gater.decision : nullptr;  // gsx_gater_enforce
     ps.seed = cfg->seed;
     ps.sharded = e->sharded() ? 1 : 0;
     {  // one-word lean calls on one engine: k_prop_hop_fast1 skips saturated receivers, and
@@ -3083,11 +3209,13 @@ int prop_begin(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_conf
     // a shard plan rewrites the reverse pairs)
     if (int rc = fanout_publish(e, msgs, m, cfg)) return rc;
     auto& K = P.fwd_key;
+    // (a new decision set under enforcement: every byte is re-evaluated; the pins follow the changed ones)
+    const uint64_t dec_gen = e->gater.enforce ? e->gater_dec_gen : 0;
     const bool fwd_same = K.valid && !e->sharded() && K.router == cfg->router && K.topic == cfg->topic &&
                           K.flood_publish == cfg->flood_publish && K.flag_gen == e->flag_gen &&
                           K.publish_threshold == e->th.publish_threshold &&
                           K.graylist_threshold == e->th.graylist_threshold && K.mem_gen == e->mem_gen &&
-                          (!need_score || K.score_gen == e->score_gen);
+                          K.dec_gen == dec_gen && (!need_score || K.score_gen == e->score_gen);
     if (fwd_same && P.fold_chg) {  // the last call's fold kept the bytes: its listed changes reach the pins
         gsx::PropState pf = ps;
         pf.inc = 1u;
@@ -3109,6 +3237,7 @@ int prop_begin(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_conf
         K.flag_gen = e->flag_gen;
         K.score_gen = e->score_gen;
         K.mem_gen = e->mem_gen;
+        K.dec_gen = dec_gen;
         K.publish_threshold = e->th.publish_threshold;
         K.graylist_threshold = e->th.graylist_threshold;
     }
@@ -4009,6 +4138,362 @@ int gsx_score_stats(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_s
     if (h_pb) HIPCHK(e, hipMemcpyAsync(out->peer_bins, d_pb, 4 * NT * nb, hipMemcpyDeviceToHost, e->stream));
     if (h_pm) HIPCHK(e, hipMemcpyAsync(out->peer_min, d_pm, 8 * NT, hipMemcpyDeviceToHost, e->stream));
     if (h_hist || h_ob || h_om || h_pb || h_pm) HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GSX_OK;
+}
+
+// ---- the peer gater (peer_gater.go) and AcceptFrom (gossipsub.go:583-594) ------
+
+// PeerGaterParams.validate, peer_gater.go:57-88
+int gsx_validate_gater_params(const gsx_gater_params* p) {
+    if (!p) return GSX_EINVAL;
+    if (!(p->threshold > 0)) return GSX_EINVAL;
+    if (!(p->global_decay > 0 && p->global_decay < 1)) return GSX_EINVAL;
+    if (!(p->source_decay > 0 && p->source_decay < 1)) return GSX_EINVAL;
+    if (p->decay_interval_ns < kSecond) return GSX_EINVAL;
+    if (!(p->decay_to_zero > 0 && p->decay_to_zero < 1)) return GSX_EINVAL;
+    // (no check of the stats retention: 0 means none is kept)
+    if (p->quiet_ns < kSecond) return GSX_EINVAL;
+    if (!(p->duplicate_weight > 0)) return GSX_EINVAL;
+    if (!(p->ignore_weight >= 1)) return GSX_EINVAL;
+    if (!(p->reject_weight >= 1)) return GSX_EINVAL;
+    return GSX_OK;
+}
+
+// DefaultPeerGaterParams, peer_gater.go:19-28, 98-116
+int gsx_default_gater_params(gsx_gater_params* p) {
+    if (!p) return GSX_EINVAL;
+    *p = gsx_gater_params{};
+    p->threshold = 0.33;
+    p->global_decay = gsx_score_parameter_decay(2 * 60 * kSecond);
+    p->source_decay = gsx_score_parameter_decay(3600 * kSecond);
+    p->decay_interval_ns = kSecond;  // DefaultDecayInterval
+    p->decay_to_zero = 0.01;         // DefaultDecayToZero
+    p->retain_stats_ns = 6 * 3600 * kSecond;
+    p->quiet_ns = 60 * kSecond;
+    p->duplicate_weight = 0.125;
+    p->ignore_weight = 1.0;
+    p->reject_weight = 16.0;
+    return GSX_OK;
+}
+
+int gsx_set_gater_params(gsx_engine* e, const gsx_gater_params* p) {
+    if (!e) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    auto& G = e->gater;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    if (e->prop.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
+    gater_free(e);  // (with the decision set and enforcement: they belonged to the old gater)
+    if (!p) return GSX_OK;
+    G.p = *p;
+    const size_t N = e->n_nodes, E = e->E;
+    int rc = 0;
+    if ((rc = dalloc(e, &G.validate, N)) || (rc = dalloc(e, &G.throttle, N)) || (rc = dalloc(e, &G.last, N)) ||
+        (rc = dalloc(e, &G.hot, N)) || (rc = dalloc(e, &G.bind, E)) || (rc = dalloc(e, &G.decision, E))) {
+        gater_free(e);
+        return rc;
+    }
+    HIPCHK(e, hipMemsetAsync(G.validate, 0, 8 * (N ? N : 1), e->stream));
+    HIPCHK(e, hipMemsetAsync(G.throttle, 0, 8 * (N ? N : 1), e->stream));
+    HIPCHK(e, hipMemsetAsync(G.hot, 0, N ? N : 1, e->stream));
+    HIPCHK(e, hipMemsetAsync(G.bind, 0xFF, 4 * (E ? E : 1), e->stream));
+    {
+        const std::vector<int64_t> never(N ? N : 1, GSX_GATER_NEVER);
+        HIPCHK(e, hipMemcpy(G.last, never.data(), 8 * never.size(), hipMemcpyHostToDevice));
+    }
+    G.on = true;
+    if ((rc = gater_grow(e))) {
+        gater_free(e);
+        return rc;
+    }
+    return GSX_OK;
+}
+
+int gsx_gater_num_groups(gsx_engine* e, uint64_t* out) {
+    if (!e || !out) return GSX_EINVAL;
+    if (!e->gater.on) return fail(e, GSX_ESTATE, "no gater (gsx_set_gater_params)");
+    *out = e->gater.groups;
+    return GSX_OK;
+}
+
+int gsx_gater_events(gsx_engine* e, const gsx_gater_event* ev, size_t n) {
+    static_assert(gsx::GATER_UNBOUND == GSX_GATER_UNBOUND && gsx::GATER_NEVER == GSX_GATER_NEVER,
+                  "the kernel's constants are the header's");
+    if (!e || (n && !ev)) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    auto& G = e->gater;
+    if (!G.on) return fail(e, GSX_ESTATE, "no gater (gsx_set_gater_params)");
+    if (n == 0) return GSX_OK;
+    if (n >= 0xFFFFFFFFull) return fail(e, GSX_EINVAL, "too many events in one call");
+    std::vector<gsx::DevGaterEvent> dev(n);
+    std::vector<uint32_t> obs(n), order(n);
+    for (size_t i = 0; i < n; ++i) {
+        const gsx_gater_event& s = ev[i];
+        if (s.pair >= e->E) return fail(e, GSX_EINVAL, "gater event pair out of range");
+        gsx::DevGaterEvent d{};
+        d.pair = s.pair;
+        d.now_ns = s.now_ns;
+        switch (s.kind) {
+            case GSX_GATER_ADD_PEER:
+                d.kind = gsx::GEV_ADD;
+                d.group = gater_group_of(e, s.pair);
+                break;
+            case GSX_GATER_REMOVE_PEER: d.kind = gsx::GEV_REMOVE; break;
+            case GSX_GATER_VALIDATE: d.kind = gsx::GEV_VALIDATE; break;
+            case GSX_GATER_DELIVER: {
+                if (s.topic >= e->T) return fail(e, GSX_EINVAL, "gater event topic out of range");
+                const double w = G.p.topic_delivery_weight[s.topic];
+                d.kind = gsx::GEV_DELIVER;
+                d.weight = w == 0 ? 1.0 : w;  // :407-411
+                break;
+            }
+            case GSX_GATER_DUPLICATE: d.kind = gsx::GEV_DUPLICATE; break;
+            case GSX_GATER_REJECT:
+                if (s.reason < GSX_REJECT_BLACKLISTED_PEER || s.reason > GSX_REJECT_SELF_ORIGIN)
+                    return fail(e, GSX_EINVAL, "unknown reject reason");
+                d.kind = (s.reason == GSX_REJECT_VALIDATION_QUEUE_FULL || s.reason == GSX_REJECT_VALIDATION_THROTTLED)
+                             ? gsx::GEV_THROTTLE
+                         : s.reason == GSX_REJECT_VALIDATION_IGNORED ? gsx::GEV_IGNORE
+                                                                     : gsx::GEV_REJECT;
+                break;
+            default: return fail(e, GSX_EINVAL, "unknown gater event kind");
+        }
+        dev[i] = d;
+        obs[i] = e->pair_obs[s.pair];
+        order[i] = (uint32_t)i;
+    }
+    // stable grouping by observer: the order inside each observer is kept
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return obs[a] < obs[b]; });
+    std::vector<gsx::DevGaterEvent> sorted(n);
+    std::vector<uint32_t> off;
+    for (size_t i = 0; i < n; ++i) {
+        sorted[i] = dev[order[i]];
+        if (i == 0 || obs[order[i]] != obs[order[i - 1]]) off.push_back((uint32_t)i);
+    }
+    const uint32_t n_og = (uint32_t)off.size();
+    off.push_back((uint32_t)n);
+    const size_t ev_bytes = sizeof(gsx::DevGaterEvent) * n, off_bytes = 4 * off.size();
+    if (G.ev_bytes < ev_bytes + off_bytes) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (G.ev) (void)hipFree(G.ev);
+        G.ev = nullptr;
+        G.ev_bytes = 0;
+        const size_t want = std::max<size_t>(2 * (ev_bytes + off_bytes), 4096);
+        HIPCHK(e, hipMalloc(&G.ev, want));
+        G.ev_bytes = want;
+    }
+    char* d = static_cast<char*>(G.ev);
+    HIPCHK(e, hipMemcpyAsync(d, sorted.data(), ev_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(d + ev_bytes, off.data(), off_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, gsx::launch_gater_events(dev_gater(e), e->d_pair_obs, reinterpret_cast<const gsx::DevGaterEvent*>(d),
+                                       reinterpret_cast<const uint32_t*>(d + ev_bytes), n_og, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (the host vectors were the copies' sources)
+    return GSX_OK;
+}
+
+int gsx_gater_decay(gsx_engine* e, int64_t now_ns) {
+    if (!e) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    if (!e->gater.on) return fail(e, GSX_ESTATE, "no gater (gsx_set_gater_params)");
+    HIPCHK(e, gsx::launch_gater_decay(dev_gater(e), now_ns, e->stream));
+    return GSX_OK;
+}
+
+int gsx_accept_from(gsx_engine* e, const uint64_t* pairs, size_t n, int64_t now_ns, uint64_t seed, uint64_t draw,
+                    uint8_t* out) {
+    static_assert(gsx::ACCEPT_NONE == GSX_ACCEPT_NONE && gsx::ACCEPT_CONTROL == GSX_ACCEPT_CONTROL &&
+                      gsx::ACCEPT_ALL == GSX_ACCEPT_ALL,
+                  "the kernel's constants are the header's");
+    if (!e || !out) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    if (!pairs && e->prop.active && e->gater.enforce)
+        return fail(e, GSX_ESTATE, "a stepped propagation is reading the decision set");
+    if (!pairs && n != e->E) return fail(e, GSX_EINVAL, "n must be the pair count when pairs is NULL");
+    for (size_t i = 0; pairs && i < n; ++i)
+        if (pairs[i] >= e->E) return fail(e, GSX_EINVAL, "pair out of range");
+    if (n == 0) return GSX_OK;
+    if (int rc = ensure_scores(e)) return rc;
+    auto& G = e->gater;
+    const bool host_out = !on_device(out);
+    gsx::AcceptArgs a{};
+    a.score = e->d_score;
+    a.pflags = e->d_pflags;
+    a.eflags = e->d_eflags;
+    a.pair_obs = e->d_pair_obs;
+    a.n = n;
+    a.graylist_threshold = e->th.graylist_threshold;
+    a.now = now_ns;
+    a.seed = seed;
+    a.draw = draw;
+    a.gater = G.on ? 1u : 0u;
+    if (pairs) {
+        if (G.list_cap < n) {
+            HIPCHK(e, hipStreamSynchronize(e->stream));
+            if (G.list_out) (void)hipFree(G.list_out);
+            if (G.list_pairs) (void)hipFree(G.list_pairs);
+            G.list_out = nullptr;
+            G.list_pairs = nullptr;
+            G.list_cap = 0;
+            const size_t want = std::max<size_t>(2 * n, 1024);
+            int rc = 0;
+            if ((rc = dalloc(e, &G.list_out, want)) || (rc = dalloc(e, &G.list_pairs, want))) return rc;
+            G.list_cap = want;
+        }
+        HIPCHK(e, hipMemcpyAsync(G.list_pairs, pairs, 8 * n, hipMemcpyHostToDevice, e->stream));
+        a.pairs = G.list_pairs;
+        a.out = host_out ? G.list_out : out;
+    } else {
+        if (!G.decision)  // (an engine without a gater keeps its decision bytes too)
+            if (int rc = dalloc(e, &G.decision, e->E)) return rc;
+        a.out = G.decision;
+    }
+    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
+    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    HIPCHK(e, gsx::launch_accept_from(dev_gater(e), a, e->stream));
+    if (region) {
+        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
+        ++e->t_used;
+    }
+    if (!pairs) {
+        G.have_decision = true;
+        G.counted = false;
+        ++e->gater_dec_gen;
+        HIPCHK(e, hipMemcpyAsync(out, G.decision, n, host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, e->stream));
+    } else if (host_out) {
+        HIPCHK(e, hipMemcpyAsync(out, G.list_out, n, hipMemcpyDeviceToHost, e->stream));
+    }
+    if (host_out || pairs) HIPCHK(e, hipStreamSynchronize(e->stream));  // (pairs: the list was the copy's source)
+    return GSX_OK;
+}
+
+int gsx_gater_export(gsx_engine* e, gsx_gater_view* v) {
+    if (!e || !v) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    auto& G = e->gater;
+    if (!G.on) return fail(e, GSX_ESTATE, "no gater (gsx_set_gater_params)");
+    const size_t N = e->n_nodes, NG = G.groups, E = e->E;
+    const auto d2h = hipMemcpyDeviceToHost;
+    if (v->validate && N) HIPCHK(e, hipMemcpyAsync(v->validate, G.validate, 8 * N, d2h, e->stream));
+    if (v->throttle && N) HIPCHK(e, hipMemcpyAsync(v->throttle, G.throttle, 8 * N, d2h, e->stream));
+    if (v->last_throttle_ns && N) HIPCHK(e, hipMemcpyAsync(v->last_throttle_ns, G.last, 8 * N, d2h, e->stream));
+    if (v->connected && NG) HIPCHK(e, hipMemcpyAsync(v->connected, G.connected, 4 * NG, d2h, e->stream));
+    if (v->expire_ns && NG) HIPCHK(e, hipMemcpyAsync(v->expire_ns, G.expire, 8 * NG, d2h, e->stream));
+    if (v->bound_group && E) HIPCHK(e, hipMemcpyAsync(v->bound_group, G.bind, 4 * E, d2h, e->stream));
+    std::vector<double> rec;
+    if ((v->deliver || v->duplicate || v->ignore || v->reject) && NG) {
+        rec.resize(4 * NG);
+        HIPCHK(e, hipMemcpyAsync(rec.data(), G.ctr, 32 * NG, d2h, e->stream));
+    }
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    double* const dst[4] = {v->deliver, v->duplicate, v->ignore, v->reject};  // GC_* order
+    for (int f = 0; f < 4 && !rec.empty(); ++f)
+        if (dst[f])
+            for (size_t g = 0; g < NG; ++g) dst[f][g] = rec[4 * g + f];
+    return GSX_OK;
+}
+
+int gsx_gater_fold_prop(gsx_engine* e) {
+    if (!e) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    auto& G = e->gater;
+    auto& P = e->prop;
+    if (!G.on) return fail(e, GSX_ESTATE, "no gater (gsx_set_gater_params)");
+    if (!P.have_last) return fail(e, GSX_ESTATE, "no propagation call yet");
+    if (P.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
+    if (e->sharded()) return fail(e, GSX_ESTATE, "the gater folds propagations of unsharded engines only");
+    gsx::PropState ps = P.last;
+    if (!ps.from_mask)
+        return fail(e, GSX_ESTATE, "first deliverers were not tracked in the last call (gsx_prop_set_tracking)");
+    ps.n_rows = P.rows_valid;
+    const uint32_t W = ps.n_words, m = ps.n_msgs;
+    if (m == 0 || e->E == 0) return GSX_OK;
+    if (P.vals.size() != m) return fail(e, GSX_ESTATE, "the last call's validation outcomes are gone");
+    if (P.cfg.topic >= e->T) return fail(e, GSX_ESTATE, "the last call's topic is not one of the engine's");
+    if (G.gcnt_groups < G.groups || !G.ocnt) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (G.gcnt) (void)hipFree(G.gcnt);
+        G.gcnt = nullptr;
+        G.gcnt_groups = 0;
+        if (int rc = dalloc(e, &G.gcnt, 4 * (size_t)G.groups)) return rc;
+        HIPCHK(e, hipMemsetAsync(G.gcnt, 0, 16 * (size_t)G.groups, e->stream));
+        G.gcnt_groups = G.groups;
+        if (!G.ocnt) {
+            if (int rc = dalloc(e, &G.ocnt, 2 * (size_t)e->n_nodes)) return rc;
+            HIPCHK(e, hipMemsetAsync(G.ocnt, 0, 8 * (size_t)e->n_nodes, e->stream));
+        }
+    }
+    std::vector<uint64_t> cls(4 * (size_t)W, 0);  // GSX_VALIDATION_* order
+    for (uint32_t k = 0; k < m; ++k) {
+        const uint32_t c = P.vals[k] <= GSX_VALIDATION_THROTTLE ? P.vals[k] : GSX_VALIDATION_ACCEPT;
+        cls[(size_t)c * W + k / 64] |= 1ull << (k % 64);
+    }
+    const size_t need = (size_t)e->E * W + cls.size();
+    if (G.fold_cap < need) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (G.fold_buf) (void)hipFree(G.fold_buf);
+        G.fold_buf = nullptr;
+        G.fold_cap = 0;
+        if (int rc = dalloc(e, &G.fold_buf, need)) return rc;
+        G.fold_cap = need;
+    }
+    uint64_t* const d_dup = G.fold_buf;
+    uint64_t* const d_cls = G.fold_buf + (size_t)e->E * W;
+    const double w = G.p.topic_delivery_weight[P.cfg.topic];
+    hipError_t st = hipMemcpyAsync(d_cls, cls.data(), 8 * cls.size(), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess) st = gsx::launch_prop_dup_rows(ps, d_dup, e->stream);
+    bool counted = false;
+    if (st == hipSuccess) {
+        st = gsx::launch_gater_fold_count(dev_gater(e), e->d_pair_obs, ps.from_mask, d_dup, d_cls, W, G.gcnt, G.ocnt,
+                                          e->stream);
+        counted = true;
+    }
+    if (st == hipSuccess)
+        st = gsx::launch_gater_fold_apply(dev_gater(e), G.gcnt, G.ocnt, w == 0 ? 1.0 : w, P.cfg.now_ns, e->stream);
+    if (st != hipSuccess && counted) {  // the counts are zero between calls, also after a failed one
+        (void)hipMemsetAsync(G.gcnt, 0, 16 * (size_t)G.gcnt_groups, e->stream);
+        (void)hipMemsetAsync(G.ocnt, 0, 8 * (size_t)e->n_nodes, e->stream);
+    }
+    const hipError_t st2 = hipStreamSynchronize(e->stream);  // (cls was the copy's source)
+    HIPCHK(e, st);
+    HIPCHK(e, st2);
+    return GSX_OK;
+}
+
+int gsx_gater_enforce(gsx_engine* e, uint32_t on) {
+    if (!e) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    auto& G = e->gater;
+    if (e->prop.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
+    if (on) {
+        if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+        if (e->sharded()) return fail(e, GSX_ESTATE, "the gater's decisions are enforced on unsharded engines only");
+        if (!G.have_decision || !G.decision)
+            return fail(e, GSX_ESTATE, "no decision set: gsx_accept_from over every pair first");
+    }
+    if (G.enforce != (on != 0)) {
+        if (int rc = fold_deferred(e)) return rc;  // deferred folds re-evaluate bytes under the setting they ran with
+        G.enforce = on != 0;
+        if (!G.enforce) e->prop.last.gdec = nullptr;
+        ++e->gater_dec_gen;
+    }
+    return GSX_OK;
+}
+
+int gsx_gater_gate_pairs(gsx_engine* e, uint64_t* none, uint64_t* control) {
+    if (!e) return GSX_EINVAL;
+    auto& G = e->gater;
+    if (!G.have_decision || !G.decision) return fail(e, GSX_ESTATE, "no decision set: gsx_accept_from over every pair first");
+    if (!G.counted) {
+        std::vector<uint8_t> d(e->E);
+        if (e->E) HIPCHK(e, hipMemcpyAsync(d.data(), G.decision, e->E, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        G.n_none = (uint64_t)std::count(d.begin(), d.end(), (uint8_t)GSX_ACCEPT_NONE);
+        G.n_control = (uint64_t)std::count(d.begin(), d.end(), (uint8_t)GSX_ACCEPT_CONTROL);
+        G.counted = true;
+    }
+    if (none) *none = G.n_none;
+    if (control) *control = G.n_control;
     return GSX_OK;
 }
 

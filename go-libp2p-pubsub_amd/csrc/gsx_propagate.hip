@@ -37,7 +37,12 @@ namespace gsx {
 // and FWD_GIN: gossipsub's AcceptFrom at the pair's observer drops every RPC
 // of the pair's neighbour (score < GraylistThreshold, not a direct peer;
 // gossipsub.go:583-594 -> pubsub.go:1014-1017: the payload is never pushed,
-// so no seen mark, no trace, no P2/P3/P4).  Floodsub and RandomSub accept all.
+// so no seen mark, no trace, no P2/P3/P4).  Under gsx_gater_enforce a pair
+// whose decision byte is AcceptControl has FWD_GIN too: pubsub.go:1019-1023
+// strips the payload of such an RPC, with the same consequences for messages.
+// So FWD_GIN = "u accepts no message from v": score < graylist OR throttled;
+// a pair without it is at or above the graylist threshold.
+// Floodsub and RandomSub accept all.
 // The score is the one of the call start, like the publishThreshold tests.
 __device__ __forceinline__ uint8_t fwd_byte(const PropState& ps, const DevState& s, uint64_t r) {
     const uint8_t pf = s.pflags[r];
@@ -65,7 +70,9 @@ __device__ __forceinline__ uint8_t fwd_byte(const PropState& ps, const DevState&
     }
     // Score() of a peer without peerStats is 0 (score.go:247-256), never below the
     // (non-positive) threshold; the score vector holds 0 for those pairs.
-    if (ps.gate && !(ef & EDGE_DIRECT) && s.score[r] < ps.graylist_threshold) out |= FWD_GIN;
+    if (ps.gate && !(ef & EDGE_DIRECT) &&
+        (s.score[r] < ps.graylist_threshold || (ps.gdec && ps.gdec[r] == 1 /* GSX_ACCEPT_CONTROL */)))
+        out |= FWD_GIN;
     return out;
 }
 
@@ -2072,8 +2079,10 @@ __global__ __launch_bounds__(256) void k_prop_defer(PropState ps, DevState s, De
     // The score a pair's own fwd byte tests (fwd_byte): none for a direct peer;
     // AcceptFrom's graylist threshold; the publish threshold too for a floodsub
     // peer or flood publishing.  Credits only raise the score, so a pair at or
-    // above its threshold keeps its byte while its sums wait; a graylisted pair
-    // (FWD_GIN) accepts no copy of the sender, so it has no credits at all.
+    // above its threshold keeps its byte while its sums wait (the gater's term of
+    // the byte, gsx_gater_enforce, does not read the score at all); a pair with
+    // FWD_GIN (graylisted, or throttled by the gater) accepts no copy of the
+    // sender, so it has no credits at all.
     const double thr_gs = ps.gate ? ps.graylist_threshold : -__builtin_inf();
     const double thr_all = ps.gate ? fmax(ps.graylist_threshold, ps.publish_threshold) : ps.publish_threshold;
     const uint64_t stride = (uint64_t)gridDim.x * 256u;
@@ -2091,9 +2100,11 @@ __global__ __launch_bounds__(256) void k_prop_defer(PropState ps, DevState s, De
             fb[i] = in ? ps.fwd[q] : 0;
         }
         // The score decides only for a floodsub peer or under flood publish: a
-        // gossipsub edge's own threshold is AcceptFrom's (FWD_GIN is exactly
-        // score < graylist on the cached scores, and such pairs are skipped), so
-        // its score is never read — most of the pass's bytes on a gossipsub overlay
+        // gossipsub edge's own threshold is AcceptFrom's (FWD_GIN holds for every
+        // pair with score < graylist on the cached scores — and for the pairs the
+        // gater throttles, which take no credits either — and such pairs are
+        // skipped; a pair without it is at or above graylist), so its score is
+        // never read — most of the pass's bytes on a gossipsub overlay
 #pragma unroll
         for (int i = 0; i < DU; ++i) {
             const uint64_t q = q0 + i * stride;

@@ -388,6 +388,85 @@ class ScoreStatsOut(C.Structure):
     ]
 
 
+# the peer gater (peer_gater.go) and AcceptFrom
+GSX_ACCEPT_NONE = 0
+GSX_ACCEPT_CONTROL = 1
+GSX_ACCEPT_ALL = 2
+GSX_GATER_NEVER = -(1 << 63)
+GSX_GATER_UNBOUND = 0xFFFFFFFF
+# gsx_gater_event_kind
+GATER_ADD_PEER = 1
+GATER_REMOVE_PEER = 2
+GATER_VALIDATE = 3
+GATER_DELIVER = 4
+GATER_DUPLICATE = 5
+GATER_REJECT = 6
+
+
+class GaterParams(C.Structure):
+    """gsx_gater_params: PeerGaterParams, peer_gater.go:31-55 (durations in ns; topic weights by index, 0 = 1)."""
+
+    _fields_ = [
+        ("threshold", C.c_double),
+        ("global_decay", C.c_double),
+        ("source_decay", C.c_double),
+        ("decay_interval_ns", C.c_int64),
+        ("decay_to_zero", C.c_double),
+        ("retain_stats_ns", C.c_int64),
+        ("quiet_ns", C.c_int64),
+        ("duplicate_weight", C.c_double),
+        ("ignore_weight", C.c_double),
+        ("reject_weight", C.c_double),
+        ("topic_delivery_weight", C.c_double * GSX_MAX_TOPICS),
+    ]
+
+
+class GaterEvent(C.Structure):
+    """gsx_gater_event"""
+
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("topic", C.c_uint32),
+        ("pair", C.c_uint64),
+        ("now_ns", C.c_int64),
+        ("reason", C.c_int32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+GATER_EVENT_DTYPE = None
+
+
+def gater_event_dtype():
+    global GATER_EVENT_DTYPE
+    if GATER_EVENT_DTYPE is None:
+        import numpy as np
+
+        GATER_EVENT_DTYPE = np.dtype(
+            [("kind", "<u4"), ("topic", "<u4"), ("pair", "<u8"), ("now_ns", "<i8"), ("reason", "<i4"),
+             ("reserved", "<u4")], align=True
+        )
+        assert GATER_EVENT_DTYPE.itemsize == C.sizeof(GaterEvent)
+    return GATER_EVENT_DTYPE
+
+
+class GaterView(C.Structure):
+    """gsx_gater_view: host addresses, None skips a member"""
+
+    _fields_ = [
+        ("validate", C.c_void_p),
+        ("throttle", C.c_void_p),
+        ("last_throttle_ns", C.c_void_p),
+        ("connected", C.c_void_p),
+        ("expire_ns", C.c_void_p),
+        ("deliver", C.c_void_p),
+        ("duplicate", C.c_void_p),
+        ("ignore", C.c_void_p),
+        ("reject", C.c_void_p),
+        ("bound_group", C.c_void_p),
+    ]
+
+
 P = C.POINTER
 _u64p = P(C.c_uint64)
 
@@ -533,6 +612,18 @@ SIGNATURES = {
     "gsx_promise_count": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
     "gsx_mcache_ids": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint64), C.c_size_t,
                                  P(C.c_size_t)]),
+    "gsx_validate_gater_params": (C.c_int, [P(GaterParams)]),
+    "gsx_default_gater_params": (C.c_int, [P(GaterParams)]),
+    "gsx_set_gater_params": (C.c_int, [C.c_void_p, P(GaterParams)]),
+    "gsx_gater_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "gsx_gater_decay": (C.c_int, [C.c_void_p, C.c_int64]),
+    # (out: a host or device address)
+    "gsx_accept_from": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "gsx_gater_export": (C.c_int, [C.c_void_p, P(GaterView)]),
+    "gsx_gater_num_groups": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
+    "gsx_gater_fold_prop": (C.c_int, [C.c_void_p]),
+    "gsx_gater_enforce": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gsx_gater_gate_pairs": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]),
     "gsx_timing_begin": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_timing_end": (
         C.c_int,

@@ -369,6 +369,73 @@ class Engine:
         self._chk(self.lib.gsx_prop_set_tracking(self.h, 1 if first_deliverers else 0), "gsx_prop_set_tracking")
         self._track = bool(first_deliverers)
 
+    # -- the peer gater and AcceptFrom (gsx.h; peer_gater.go, gossipsub.go:583-594) --------
+    def set_gater_params(self, p: "abi.GaterParams | None"):
+        """gsx_set_gater_params: a fresh gater for the loaded overlay; None drops it."""
+        self._chk(self.lib.gsx_set_gater_params(self.h, C.byref(p) if p is not None else None), "gsx_set_gater_params")
+
+    def gater_events(self, events):
+        """gsx_gater_events: rows of abi.gater_event_dtype() (kind, topic, pair, now_ns, reason),
+        applied per observer in the order given."""
+        ev = np.ascontiguousarray(events, dtype=abi.gater_event_dtype())
+        self._chk(self.lib.gsx_gater_events(self.h, ev.ctypes.data_as(C.c_void_p), len(ev)), "gsx_gater_events")
+
+    def gater_decay(self, now: int):
+        self._chk(self.lib.gsx_gater_decay(self.h, now), "gsx_gater_decay")
+
+    def accept_from(self, now: int, seed: int, draw: int, pairs=None, out_ptr=None):
+        """gsx_accept_from -> [n] u8 of GSX_ACCEPT_* for `pairs` (None: every pair, which also
+        leaves the decision bytes on the device).  out_ptr: a device pointer or tensor written
+        in stream order; then -> None."""
+        if pairs is None:
+            pp, n = None, self.n_pairs
+        else:
+            pa = np.ascontiguousarray(pairs, dtype=np.uint64).reshape(-1)
+            pp, n = pa.ctypes.data_as(C.c_void_p), len(pa)
+        if out_ptr is not None:
+            self._chk(self.lib.gsx_accept_from(self.h, pp, n, now, seed, draw, self._p(out_ptr)), "gsx_accept_from")
+            return None
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        self._chk(self.lib.gsx_accept_from(self.h, pp, n, now, seed, draw, out.ctypes.data_as(C.c_void_p)),
+                  "gsx_accept_from")
+        return out[:n]
+
+    def gater_num_groups(self) -> int:
+        v = C.c_uint64()
+        self._chk(self.lib.gsx_gater_num_groups(self.h, C.byref(v)), "gsx_gater_num_groups")
+        return int(v.value)
+
+    def gater_export(self) -> dict:
+        """gsx_gater_export -> dict of arrays: validate, throttle, last_throttle_ns [n_nodes];
+        connected, expire_ns, deliver, duplicate, ignore, reject [gater_num_groups()] (group
+        u < n_nodes: observer u's unknown-IP group, n_nodes + g: the engine's (observer, IP)
+        group g); bound_group [n_pairs] (GSX_GATER_UNBOUND: none)."""
+        n, g, e = self.n_nodes, self.gater_num_groups(), self.n_pairs
+        a = {
+            "validate": np.zeros(n), "throttle": np.zeros(n), "last_throttle_ns": np.zeros(n, dtype=np.int64),
+            "connected": np.zeros(g, dtype=np.uint32), "expire_ns": np.zeros(g, dtype=np.int64),
+            "deliver": np.zeros(g), "duplicate": np.zeros(g), "ignore": np.zeros(g), "reject": np.zeros(g),
+            "bound_group": np.zeros(e, dtype=np.uint32),
+        }
+        v = abi.GaterView(**{k: (x.ctypes.data if x.size else None) for k, x in a.items()})
+        self._chk(self.lib.gsx_gater_export(self.h, C.byref(v)), "gsx_gater_export")
+        return a
+
+    def gater_fold_prop(self):
+        """gsx_gater_fold_prop: the last propagation's receipts as the gater's tracer calls."""
+        self._chk(self.lib.gsx_gater_fold_prop(self.h), "gsx_gater_fold_prop")
+
+    def gater_enforce(self, on: bool):
+        """gsx_gater_enforce: gossipsub propagation drops the payload of pairs the last full
+        accept_from answered GSX_ACCEPT_CONTROL."""
+        self._chk(self.lib.gsx_gater_enforce(self.h, 1 if on else 0), "gsx_gater_enforce")
+
+    def gater_gate_pairs(self):
+        """gsx_gater_gate_pairs -> (pairs with ACCEPT_NONE, pairs with ACCEPT_CONTROL) of the decision set."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.gsx_gater_gate_pairs(self.h, C.byref(a), C.byref(b)), "gsx_gater_gate_pairs")
+        return int(a.value), int(b.value)
+
     # -- stepped / sharded propagation (gsx.h "range sharding") --------------------------
     def load_overlay_shard(self, n_total, node_lo, row_ptr, col, edge_flags=None, node_ips=None):
         row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)

@@ -539,7 +539,9 @@ typedef struct gsx_prop_out {
     uint64_t rejected;       /* receipts of REJECT messages (RejectMessage, P4 to the sender) */
     uint64_t ignored;        /* receipts of IGNORE / THROTTLE messages                      */
     uint64_t graylisted;     /* copies dropped by the receiver's AcceptFrom (gossipsub only):
-                              * sender not direct and scored below GraylistThreshold       */
+                              * sender not direct and scored below GraylistThreshold, or,
+                              * under gsx_gater_enforce, throttled by the peer gater
+                              * (AcceptControl): copies dropped for either reason        */
 } gsx_prop_out;
 
 /* credit_scores values */
@@ -1186,6 +1188,182 @@ int gsx_mcache_put(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_
  * per-launch durations (ms) and their count. */
 int gsx_timing_begin(gsx_engine* e, uint32_t max_launches);
 int gsx_timing_end(gsx_engine* e, double* total_ms, double* min_ms, double* max_ms, uint32_t* n_launches);
+
+/* ---- the peer gater and AcceptFrom (peer_gater.go, gossipsub.go:583-594) ------ */
+/* WithPeerGater's reactive validation-queue management: per observer the
+ * validate / throttle counters and the time of the last throttle
+ * (peer_gater.go:127-131), per (observer, IP) the connected count, the expiry
+ * and the deliver / duplicate / ignore / reject counters
+ * (peerGaterStats, :143-151).  The gater is a RawTracer of its own: its
+ * AddPeer / RemovePeer and message traces arrive through gsx_gater_events and
+ * are independent of the scorer's (gsx_apply_events).
+ *
+ * Groups.  A gater group is an (observer, IP) pair: group n_nodes + g is the
+ * engine's (observer, IP) group g (the P6 groups; new ones appear when
+ * gsx_set_pair_ips brings an observer a new IP), group u < n_nodes is observer
+ * u's "<unknown>" group (:297-298) for peers without an IP.  A pair's group is
+ * the group of its first IP id (the gater follows one IP per peer, getPeerIP
+ * :280-317): slot 0 of its IP list, slot 1 if slot 0 is GSX_NO_IP.  A pair is
+ * BOUND to the group it had at its GSX_GATER_ADD_PEER until its
+ * GSX_GATER_REMOVE_PEER (pg.peerStats[p] keeps the pointer): a later
+ * gsx_set_pair_ips does not rebind it.
+ *
+ * Differences from the reference, both unreachable from a router (it never
+ * traces a peer it has not added): a pair-level event (REMOVE_PEER, DELIVER,
+ * DUPLICATE, ignored / failed REJECT) for an unbound pair is ignored, where
+ * getPeerStats (:261-268) would create a stats object with connected == 0 that
+ * the next decay orphans; an expired group is zeroed in place, where
+ * decayStats deletes the map entry (a later AddPeer finds zeros either way).
+ * rand.Float64() (:357) is replaced by the counter hash, see gsx_accept_from.
+ *
+ * Out of scope: range shards and message-parallel replicas for enforcement
+ * and the fold (the per-observer state itself needs no exchange, so the other
+ * calls work on a shard); the ThrottlePeer trace (pubsub.go:1023) that drops
+ * the gossip tracer's promises (gsx_promise_throttle exists for a caller); the
+ * heartbeat's control RPCs (AcceptControl keeps them: nothing changes there);
+ * a C++ pubsub::PeerGater mirror in gsx_pubsub.hpp. */
+typedef struct gsx_gater_params { /* PeerGaterParams, peer_gater.go:31-55 */
+    double threshold;
+    double global_decay;
+    double source_decay;
+    int64_t decay_interval_ns;
+    double decay_to_zero;
+    int64_t retain_stats_ns;
+    int64_t quiet_ns;
+    double duplicate_weight;
+    double ignore_weight;
+    double reject_weight;
+    double topic_delivery_weight[GSX_MAX_TOPICS]; /* TopicDeliveryWeights by topic index; 0 means 1 (:407-411) */
+} gsx_gater_params;
+
+/* PeerGaterParams.validate (:57-88): 0 or GSX_EINVAL. */
+int gsx_validate_gater_params(const gsx_gater_params* p);
+/* DefaultPeerGaterParams (:19-28, 98-116); no topic weights. */
+int gsx_default_gater_params(gsx_gater_params* out);
+/* newPeerGater (:193-202) for the loaded overlay: empty state, nobody bound,
+ * last throttle "never".  NULL drops the gater (the default: AcceptFrom's
+ * third stage then accepts).  Like the other setters it does not validate.
+ * Loading an overlay drops the gater.  GSX_ESTATE: no overlay loaded. */
+int gsx_set_gater_params(gsx_engine* e, const gsx_gater_params* p);
+
+enum gsx_gater_event_kind {
+    GSX_GATER_ADD_PEER = 1,    /* AddPeer :369-375: bind the pair, connected++                     */
+    GSX_GATER_REMOVE_PEER = 2, /* RemovePeer :377-386: connected--, expire = now + RetainStats, unbind */
+    GSX_GATER_VALIDATE = 3,    /* ValidateMessage :393-398: the observer's validate++              */
+    GSX_GATER_DELIVER = 4,     /* DeliverMessage :400-414: deliver += weight(topic)                */
+    GSX_GATER_DUPLICATE = 5,   /* DuplicateMessage :437-443: duplicate++                           */
+    GSX_GATER_REJECT = 6       /* RejectMessage :416-435 by `reason` (gsx_reject_reason): queue full
+                                  or throttled: the observer's throttle++, last throttle = now;
+                                  ignored: ignore++; any other reason: reject++                  */
+};
+
+/* `pair` names (observer, ReceivedFrom peer); VALIDATE and a throttling REJECT
+ * use its observer only.  `topic` is read by DELIVER, `reason` by REJECT,
+ * `now_ns` by REMOVE_PEER and a throttling REJECT. */
+typedef struct gsx_gater_event {
+    uint32_t kind;
+    uint32_t topic;
+    uint64_t pair;
+    int64_t now_ns;
+    int32_t reason;
+    uint32_t reserved;
+} gsx_gater_event;
+
+/* Applies the events on the device, per observer in the order given.  An
+ * ADD_PEER of a bound pair counts again on the group it is bound to, as
+ * getPeerStats does.  GSX_EINVAL: a NULL argument, a pair out of range, an
+ * unknown kind or reject reason, a DELIVER topic >= n_topics (nothing is
+ * applied).  GSX_ESTATE: no gater. */
+int gsx_gater_events(gsx_engine* e, const gsx_gater_event* ev, size_t n);
+/* decayStats (:219-259), the gater's ticker every DecayInterval: validate and
+ * throttle of every observer by GlobalDecay, the four counters of every group
+ * with connected > 0 by SourceDecay, each zeroed below DecayToZero; a group
+ * with connected == 0 is not decayed and is zeroed when expire < now_ns. */
+int gsx_gater_decay(gsx_engine* e, int64_t now_ns);
+
+#define GSX_ACCEPT_NONE 0u    /* AcceptNone    pubsub.go AcceptStatus */
+#define GSX_ACCEPT_CONTROL 1u /* AcceptControl */
+#define GSX_ACCEPT_ALL 2u     /* AcceptAll     */
+
+/* The whole GossipSubRouter.AcceptFrom (gossipsub.go:583-594) for pairs[0..n)
+ * (pairs == NULL: every pair, n = the pair count), one status byte each into
+ * out (host or device memory, as gsx_score_stats takes its outputs: device
+ * memory is written in stream order with no host synchronisation):
+ *   1. a direct peer (GSX_EDGE_DIRECT): ALL;
+ *   2. score < GraylistThreshold: NONE, on the scores exactly as gsx_scores
+ *      would return them (the same settling first);
+ *   3. peerGater.AcceptFrom (:320-363): ALL when the observer's last throttle
+ *      is more than Quiet before now_ns (or never happened), when throttle
+ *      == 0, when validate != 0 and throttle / validate < Threshold, when the
+ *      group's total = deliver + DuplicateWeight * duplicate + IgnoreWeight *
+ *      ignore + RejectWeight * reject is 0, and when u < (1 + deliver) /
+ *      (1 + total); else CONTROL.  u = (h4(seed, 14, pair, draw) >> 11) *
+ *      2^-53 with h4 the counter hash of the other draws (tag 14), the shape of
+ *      Go's Int63n(1 << 53) / 2^53.  A pair the scorer holds no peerStats for,
+ *      an unbound pair, and an engine without a gater pass this stage with ALL.
+ * The result of a call over every pair stays on the device as the decision
+ * bytes.  Both divisions are IEEE binary64 divisions, the sum is evaluated in
+ * the source's order without contraction: the bytes equal the reference's for
+ * the same u.  GSX_EINVAL: NULL out, n != pairs with pairs NULL, a pair out of
+ * range.  GSX_ESTATE: no overlay loaded. */
+int gsx_accept_from(gsx_engine* e, const uint64_t* pairs, size_t n, int64_t now_ns, uint64_t seed, uint64_t draw,
+                    uint8_t* out);
+
+/* The gater's state, for tests, checkpoints and inspection tooling.  NULL
+ * members are skipped.  Per observer (n_nodes): validate, throttle,
+ * last_throttle_ns (GSX_GATER_NEVER before the first throttle); per group
+ * (gsx_gater_num_groups): connected, expire_ns and the four counters; per
+ * pair: the group it is bound to, GSX_GATER_UNBOUND for none. */
+#define GSX_GATER_NEVER INT64_MIN
+#define GSX_GATER_UNBOUND 0xFFFFFFFFu
+typedef struct gsx_gater_view {
+    double* validate;
+    double* throttle;
+    int64_t* last_throttle_ns;
+    uint32_t* connected;
+    int64_t* expire_ns;
+    double* deliver;
+    double* duplicate;
+    double* ignore;
+    double* reject;
+    uint32_t* bound_group;
+} gsx_gater_view;
+int gsx_gater_export(gsx_engine* e, gsx_gater_view* v);
+int gsx_gater_num_groups(gsx_engine* e, uint64_t* out);
+
+/* Folds the last gossipsub / floodsub / randomsub propagation of an unsharded
+ * engine into the gater, as the tracer calls of that batch would have, defined
+ * on the call's public results.  For pair p = (u -> v), "first receipt" = a
+ * message k with first_from(k, u) == v (gsx_prop_results):
+ *   deliver   += weight(topic) per first receipt of an ACCEPT message,
+ *   reject    += 1 per first receipt of a REJECT message (validation failed),
+ *   ignore    += 1 per first receipt of an IGNORE message,
+ *   duplicate += 1 per bit of p's row of gsx_prop_duplicates
+ * on the group p is bound to (an unbound pair's are dropped), and at u
+ *   validate  += 1 per first receipt, whatever the outcome (validation.go Push),
+ *   throttle  += 1 per first receipt of a THROTTLE message, last throttle = the
+ *                call's now_ns if there was one.
+ * The counts are gathered per group and per observer as integers (integer
+ * atomics) and applied by one lane each: every step of one kind is the same
+ * addend, so the result equals the steps in any order and is bit-identical
+ * from run to run.  GSX_ESTATE: no gater, no propagation yet, a stepped call
+ * in flight, a range shard, or first-deliverer tracking off in that call. */
+int gsx_gater_fold_prop(gsx_engine* e);
+
+/* While on, a gossipsub propagation call treats a pair whose decision byte is
+ * GSX_ACCEPT_CONTROL like a graylisted one (pubsub.go:1019-1023: the payload
+ * of the sender's RPCs is never pushed: no seen mark, no trace, no credit);
+ * gsx_prop_out.graylisted then counts the copies dropped for either reason.
+ * The bytes are those of the last gsx_accept_from over every pair; a call
+ * after a new one re-evaluates every pair's forwarding byte.  Floodsub and
+ * RandomSub accept everything, as before.  A decision set belongs to the gater
+ * it was computed under: gsx_set_gater_params (also with NULL) and loading an
+ * overlay drop it and turn enforcement off.  GSX_ESTATE (turning it on): a
+ * range shard, or no decision set; a stepped propagation in flight. */
+int gsx_gater_enforce(gsx_engine* e, uint32_t on);
+/* Pairs with GSX_ACCEPT_NONE / GSX_ACCEPT_CONTROL in the decision set (either
+ * pointer may be NULL).  GSX_ESTATE: no decision set. */
+int gsx_gater_gate_pairs(gsx_engine* e, uint64_t* none, uint64_t* control);
 
 #ifdef __cplusplus
 }
