@@ -25,7 +25,7 @@ def params(**kw):
 
 
 def exchange_run(be, n=300, d=6, T=2, seed=5, ticks=8, hops=2, msgs=24, invalid=0.0, exchange_from=0, prefill=0,
-                 runner=None, credit=None, window_ms=None, latency_ms=5, delay_ms=0.0, **gp_kw):
+                 runner=None, credit=None, window_ms=None, latency_ms=5, delay_ms=0.0, topics=None, **gp_kw):
     """pc.setup's random mesh; every round: a heartbeat (with the exchange),
     then a gossipsub batch that travels only `hops` hops (so most nodes miss
     it and learn of it by IHAVE), then a refresh.  Rounds before
@@ -37,7 +37,8 @@ def exchange_run(be, n=300, d=6, T=2, seed=5, ticks=8, hops=2, msgs=24, invalid=
     old copy outside by the next heartbeat); latency_ms / delay_ms: the
     batches' hop latency and validation delay (an old copy was validated at
     the batch's now + hop * (latency + delay), or at the heartbeat that
-    recovered it).
+    recovered it); topics: round k's batch goes on topics[k % len(topics)]
+    instead of topic k % T.
     Returns per-tick counters
     and snapshots (records, backoff, scores, IHAVEs) plus every node's cached
     ids after the last round."""
@@ -66,7 +67,8 @@ def exchange_run(be, n=300, d=6, T=2, seed=5, ticks=8, hops=2, msgs=24, invalid=
         else:
             outs.append(runner.heartbeat(1 + k, now, seed * 31 + 7)[0])
         snaps.append(hc.snapshot(be))
-        cfg = pc.config(abi.GSX_ROUTER_GOSSIPSUB, topic=k % T, max_hops=hops, latency_ms=latency_ms, seed=seed + k,
+        topic = k % T if topics is None else topics[k % len(topics)]
+        cfg = pc.config(abi.GSX_ROUTER_GOSSIPSUB, topic=topic, max_hops=hops, latency_ms=latency_ms, seed=seed + k,
                         delay_ms=delay_ms)
         if credit is not None:
             cfg.credit_scores = credit

@@ -24,9 +24,11 @@ def snapshot(be):
 
 
 def mesh_run(be, n, d, T, seed, ticks, mesh_degree=6, mix=False, direct=0.0, disconnect=0.0, gp=None,
-             prop_msgs=0, first_tick=1, mostly_positive=False):
+             prop_msgs=0, first_tick=1, mostly_positive=False, prop_topics=None, pre=None):
     """pc.setup's random mesh, then `ticks` rounds of: heartbeat, optional
-    gossipsub propagation with score credits, refresh.  Returns the per-tick
+    gossipsub propagation with score credits, refresh.  Round k propagates on
+    topic k % T, or on prop_topics[k % len(prop_topics)] if given; pre: a list
+    that gets the exported state before the first round.  Returns the per-tick
     counters and snapshots."""
     ov = pc.overlay(n, d, seed, mix_protocols=mix, direct_frac=direct)
     pc.setup(be, ov, T, seed, mesh_degree=mesh_degree, disconnect_frac=disconnect)
@@ -36,6 +38,8 @@ def mesh_run(be, n, d, T, seed, ticks, mesh_degree=6, mix=False, direct=0.0, dis
         be.set_app_scores(np.where(rng.random(E) < 0.08, -500.0, np.abs(rng.normal(0, 2, E))))
     if gp is not None:
         be.set_gossipsub_params(gp)
+    if pre is not None:
+        pre.append(be.export_state())
     outs, snaps = [], []
     for k in range(ticks):
         tick = first_tick + k
@@ -43,7 +47,8 @@ def mesh_run(be, n, d, T, seed, ticks, mesh_degree=6, mix=False, direct=0.0, dis
         outs.append(be.heartbeat(tick, now, seed * 31 + 7).as_dict())
         snaps.append(snapshot(be))
         if prop_msgs:
-            cfg = pc.config(abi.GSX_ROUTER_GOSSIPSUB, topic=k % T, latency_ms=5, seed=seed + k)
+            topic = k % T if prop_topics is None else prop_topics[k % len(prop_topics)]
+            cfg = pc.config(abi.GSX_ROUTER_GOSSIPSUB, topic=topic, latency_ms=5, seed=seed + k)
             cfg.now_ns = now + 100 * MS
             be.propagate(pc.messages(n, prop_msgs, seed + 1000 * k), cfg)
         be.refresh(now + 500 * MS)

@@ -103,10 +103,11 @@ def px_run(be, n, d, T, seed, ticks, mesh_degree=14, no_px_frac=0.1, accept_px=0
     return ov, outs, recs, snaps
 
 
-def px_member_run(be, n=500, d=8, T=2, seed=13):
+def px_member_run(be, n=500, d=8, T=2, seed=13, leave_topic=0, join_topic=None):
     """PX in Join / Leave rounds (gsx.h): a mesh with partial subscriptions,
     some nodes leave a topic (every Leave PRUNE carries PX), others join one
-    (their GRAFTs' answers may).  Returns per-call (counters, px records)."""
+    (their GRAFTs' answers may); by default topic 0 is left and topic 1 joined
+    (topic 0 when T = 1).  Returns per-call (counters, px records)."""
     ov = pc.overlay(n, d, seed, mix_protocols=True, direct_frac=0.02)
     rng = np.random.default_rng(seed + 5)
     pc.setup(be, ov, T, seed, mesh_degree=4, disconnect_frac=0.02)
@@ -122,11 +123,14 @@ def px_member_run(be, n=500, d=8, T=2, seed=13):
     res = []
     now = T0 + 3 * S
     res.append((be.heartbeat(1, now, seed).as_dict(), be.hb_px_records()))
-    leavers = np.nonzero((joined & np.uint64(1)) != 0)[0][:40].astype(np.uint32)
-    out = be.leave(leavers, np.zeros(len(leavers), dtype=np.uint32), now + S)
+    leavers = np.nonzero((joined & (np.uint64(1) << np.uint64(leave_topic))) != 0)[0][:40].astype(np.uint32)
+    out = be.leave(leavers, np.full(len(leavers), leave_topic, dtype=np.uint32), now + S)
     res.append((out.as_dict(), be.hb_px_records()))
-    joiners = np.nonzero((joined & np.uint64(2)) == 0)[0][:40].astype(np.uint32)
-    out = be.join(joiners, np.ones(len(joiners), dtype=np.uint32) if T > 1 else np.zeros(len(joiners), dtype=np.uint32),
-                  now + 2 * S, seed + 1)
+    if join_topic is None:
+        jbit, join_topic = 1, (1 if T > 1 else 0)
+    else:
+        jbit = join_topic
+    joiners = np.nonzero((joined & (np.uint64(1) << np.uint64(jbit))) == 0)[0][:40].astype(np.uint32)
+    out = be.join(joiners, np.full(len(joiners), join_topic, dtype=np.uint32), now + 2 * S, seed + 1)
     res.append((out.as_dict(), be.hb_px_records()))
     return res

@@ -128,8 +128,10 @@ def make_ops(ov, n_topics, seed, n_steps=400):
             app[rng.random(E) < 0.5] = 0.0
             ops.append(("app", app))
         elif r < 0.90:
-            t = int(rng.integers(0, n_topics - 1))
-            _, tps = scenario_params(n_topics)
+            # (n_topics = 1: scenario_params scores no topic; the op then carries topic 0's
+            # parameters of the two-topic scenario, for callers that score topic 0 themselves)
+            t = int(rng.integers(0, max(n_topics - 1, 1)))
+            _, tps = scenario_params(max(n_topics, 2))
             tp = tps[t]
             tp.first_message_deliveries_cap = float(rng.integers(3, 12))
             tp.mesh_message_deliveries_cap = float(rng.integers(3, 12))
@@ -155,8 +157,11 @@ def make_ops(ov, n_topics, seed, n_steps=400):
     return ops
 
 
-def replay(be, ov, n_topics, ops, whitelist=(3,)):
+def replay(be, ov, n_topics, ops, whitelist=(3,), topic_params=None):
+    """topic_params: {topic: TopicScoreParams} to start from instead of scenario_params'."""
     pp, tps = scenario_params(n_topics)
+    if topic_params is not None:
+        tps = topic_params
     be.set_peer_params(pp)
     for t, tp in tps.items():
         be.set_topic_params(t, tp)
