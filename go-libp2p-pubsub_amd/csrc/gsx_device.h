@@ -15,6 +15,7 @@ struct DevTopicParams {
     double topic_weight;
     double w1, cap1;  // P1 weight / cap
     int64_t q1;       // TimeInMeshQuantum (ns)
+    double inv_q1;    // q1_inverse(q1): div_q1's estimate (gsx_ops.h); 0 = always the plain division
     double w2, d2, cap2;
     double w3, d3, cap3, thr3;
     int64_t win3, act3;  // window, activation (ns)
@@ -23,6 +24,10 @@ struct DevTopicParams {
     int32_t scored;
     int32_t pad;
 };
+
+// DevTopicParams::inv_q1 for a quantum: 1 / q1 rounded once, or 0 for a quantum
+// below zero (div_q1, gsx_ops.h, then always divides plainly).
+__host__ __device__ __forceinline__ double q1_inverse(int64_t q1) { return q1 > 0 ? 1.0 / (double)q1 : 0.0; }
 
 // Global parameters (PeerScoreParams, score_params.go:53-96) passed by value.
 struct DevPeerParams {

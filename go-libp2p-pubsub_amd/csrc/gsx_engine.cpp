@@ -680,6 +680,7 @@ gsx::DevTopicParams dev_topic_params(const gsx_engine* e, uint32_t t) {
     d.w1 = p.time_in_mesh_weight;
     d.cap1 = p.time_in_mesh_cap;
     d.q1 = e->scored[t] ? p.time_in_mesh_quantum_ns : 1;  // unscored topics are skipped, never divided by
+    d.inv_q1 = gsx::q1_inverse(d.q1);
     d.w2 = p.first_message_deliveries_weight;
     d.d2 = p.first_message_deliveries_decay;
     d.cap2 = p.first_message_deliveries_cap;

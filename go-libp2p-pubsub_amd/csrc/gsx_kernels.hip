@@ -76,6 +76,8 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
     const uint32_t phase = s.phase;
     const bool wb = REFRESH && phase + 1 >= s.wb_period;
     const bool lag = st & PAIR_CONNECTED;
+    // what a connected pair's flag byte keeps at a refresh
+    const uint8_t keep_conn = (uint8_t)~(REC_FRESH | (wb ? REC_EPOCH : 0));
     double* const tile = s.rec + (p / TILE) * (uint64_t)T * (NFIELD * TILE) + lane;
     uint8_t* const ftile = s.rflags + (p / TILE) * (uint64_t)T * TILE + lane;
     double score = 0.0;
@@ -84,38 +86,49 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
     auto topic_step = [&](int t, const DevTopicParams& tp, double fmd, double mmd, double mfp, double imd,
                           int64_t graft, uint8_t fl, uint32_t zmt) {
         double* const r = tile + (uint64_t)t * (NFIELD * TILE);
-        int64_t mt = 0;
         const double fmd0 = fmd, mmd0 = mmd, mfp0 = mfp, imd0 = imd;
         // the pending decays, and this refresh's: the same multiply and compare
-        // in the same order as a store after each would have seen (wave-uniform
-        // bound unless an event touched a lane's record since the last store)
+        // in the same order as a store after each would have seen.  When every
+        // lane has the same count the loop is counted in a scalar register,
+        // with no per-lane mask to keep; the counts differ only where an event
+        // touched a lane's record since the last store, or the wave mixes
+        // connected and retained pairs.
         const uint32_t nd = (lag ? (phase - ((uint32_t)fl >> REC_EPOCH_SHIFT)) & 3u : 0u) + (conn ? 1u : 0u);
-        for (uint32_t i = 0; i < nd; ++i) {
+        const uint32_t nd0 = __builtin_amdgcn_readfirstlane(nd);
+        auto decay_all = [&]() {
             fmd = decay(fmd, tp.d2, pp.decay_to_zero);
             mmd = decay(mmd, tp.d3, pp.decay_to_zero);
             mfp = decay(mfp, tp.d3b, pp.decay_to_zero);
             imd = decay(imd, tp.d4, pp.decay_to_zero);
+        };
+        if (__ballot(nd != nd0) == 0) {
+            for (uint32_t i = 0; i < nd0; ++i) decay_all();
+        } else {
+            for (uint32_t i = 0; i < nd; ++i) decay_all();
         }
+        // a counter that decays is written back only if it changed: a zero
+        // counter (most peers never send an invalid message, most meshes never
+        // fail) decays to itself, and a wave whose 64 lanes all hold zero skips
+        // the 512-B store entirely
+        if (wb) {
+            if (conn && __double_as_longlong(fmd) != __double_as_longlong(fmd0)) __builtin_nontemporal_store(fmd, r + FMD * TILE);
+            if (conn && __double_as_longlong(mmd) != __double_as_longlong(mmd0)) __builtin_nontemporal_store(mmd, r + MMD * TILE);
+            if (conn && __double_as_longlong(mfp) != __double_as_longlong(mfp0)) __builtin_nontemporal_store(mfp, r + MFP * TILE);
+            if (conn && __double_as_longlong(imd) != __double_as_longlong(imd0)) __builtin_nontemporal_store(imd, r + IMD * TILE);
+        }
+        // meshTime, activation and the flag byte (:544-549).  One branch on the
+        // pair's state (nearly always the same in the whole wave); inside it
+        // selects: a connected pair's in-mesh record counts from `now` and may
+        // become active, and its flags lose FRESH (and the epoch, when this
+        // refresh stored: as of the new phase, 0).  A retained pair's stand.
+        const bool in_mesh = fl & REC_IN_MESH;
+        int64_t mt = 0;
         if (conn) {
-            uint8_t nf = fl & ~REC_FRESH;
-            if (wb) {
-                // a counter that decays is written back only if it changed: a
-                // zero counter (most peers never send an invalid message, most
-                // meshes never fail) decays to itself, and a wave whose 64 lanes
-                // all hold zero skips the 512-B store entirely
-                if (__double_as_longlong(fmd) != __double_as_longlong(fmd0)) __builtin_nontemporal_store(fmd, r + FMD * TILE);
-                if (__double_as_longlong(mmd) != __double_as_longlong(mmd0)) __builtin_nontemporal_store(mmd, r + MMD * TILE);
-                if (__double_as_longlong(mfp) != __double_as_longlong(mfp0)) __builtin_nontemporal_store(mfp, r + MFP * TILE);
-                if (__double_as_longlong(imd) != __double_as_longlong(imd0)) __builtin_nontemporal_store(imd, r + IMD * TILE);
-                nf &= ~REC_EPOCH;  // stored as of the new phase, 0
-            }
-            if (fl & REC_IN_MESH) {  // :544-549
-                mt = now - graft;
-                if (mt > tp.act3) nf |= REC_ACTIVE;
-            }
+            mt = in_mesh ? now - graft : 0;
+            const uint8_t nf = (uint8_t)((fl & keep_conn) | ((in_mesh && mt > tp.act3) ? REC_ACTIVE : 0));
             if (nf != fl) ftile[t * TILE] = nf;  // rare once the mesh is steady
             fl = nf;
-        } else if ((fl & REC_IN_MESH) && !(fl & REC_FRESH)) {
+        } else if (in_mesh && !(fl & REC_FRESH)) {
             mt = s.last_refresh - graft;
         }
         if constexpr (REFRESH) {

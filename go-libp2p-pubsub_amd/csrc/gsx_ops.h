@@ -47,12 +47,59 @@ __device__ __forceinline__ double score_tail(const DevState& s, const DevPeerPar
     return score;
 }
 
-// One topic's contribution, score.go:276-311.
+// ---- P1's Duration division (score.go:280) ------------------------------------
+// mesh_time / q1 as Go's int64 division (truncating), without the compiler's
+// 64-bit software divide on the device.  The host stores inv = q1_inverse(q1)
+// (gsx_device.h) beside q1 (DevTopicParams); inv == 0 (q1 < 0, which only a
+// topic with TimeInMeshWeight == 0 can have) always takes the plain division.
+//
+// For q1 > 0 and |mt| < 2^50 (13 days in ns), with x = mt / q1 the real quotient
+// and u = 2^-53:
+//   (double)mt is exact; (double)q1 = q1 (1 + d1), inv = (1 + d2) / (double)q1,
+//   est = mt * inv * (1 + d3), |d_i| <= u, so |est - x| <= |x| ((1 + u)^2 / (1 - u) - 1)
+//   < |x| * 3.0001 u < 2^50 * 3.0001 * 2^-53 < 0.3751;
+//   est + 1.5 * 2^52 rounds est to an integer n (|est| < 2^51, ties to even):
+//   |n - est| <= 0.5, and n is the sum's low 52 mantissa bits less 2^51.
+// So |n - x| < 0.8751 < 1: n is within 1 of trunc(x), and one exact integer
+// remainder r = mt - n * q1 says which way: trunc(x) leaves a remainder of mt's
+// sign with |r| < q1.  n * q1 does not overflow: n != 0 needs |x| > 0.1249, hence
+// q1 < 2^53 and |n * q1| <= |mt| + 0.8751 * q1 < 2^54.
+// Outside the bound the branch to the plain division is taken by the lanes that
+// need it (a wave without such a lane skips it).  With inv == 0 every lane that
+// divides takes it: such a topic runs at the software divide's speed, as it
+// did before, and only for its in-mesh records (topic_score).
+constexpr int64_t DIV_Q1_BOUND = 1ll << 50;
+
+__host__ __device__ __forceinline__ int64_t div_q1(int64_t mt, int64_t q1, double inv) {
+    // |mt| < 2^50 as one unsigned compare: mt + 2^50 in [1, 2^51)
+    if (inv != 0.0 && (uint64_t)mt + (uint64_t)DIV_Q1_BOUND - 1u < 2u * (uint64_t)DIV_Q1_BOUND - 1u) {
+        const double est = (double)mt * inv;
+        const double sum = est + 6755399441055744.0;  // 1.5 * 2^52
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint64_t bits = (uint64_t)__double_as_longlong(sum);
+#else
+        uint64_t bits;
+        __builtin_memcpy(&bits, &sum, sizeof bits);
+#endif
+        int64_t n = (int64_t)(bits & ((1ull << 52) - 1)) - (1ll << 51);
+        const int64_t r = (int64_t)((uint64_t)mt - (uint64_t)n * (uint64_t)q1);
+        const bool neg = mt < 0;
+        const bool up = neg ? r > 0 : r >= q1;     // n is one below trunc(x)
+        const bool down = neg ? r <= -q1 : r < 0;  // n is one above
+        n += (int64_t)up - (int64_t)down;
+        return n;
+    }
+    return mt / q1;
+}
+
+// One topic's contribution, score.go:276-311.  P1 and P3 are computed only for
+// the records that have them (in the mesh; active and under the threshold), as
+// the reference does: a record outside the mesh never reaches the division.
 __device__ __forceinline__ double topic_score(const DevTopicParams& tp, uint8_t fl, int64_t mesh_time, double fmd,
                                               double mmd, double mfp, double imd) {
     double ts = 0.0;
     if (fl & REC_IN_MESH) {  // P1, integer Duration division (:280)
-        double p1 = (double)(mesh_time / tp.q1);
+        double p1 = (double)div_q1(mesh_time, tp.q1, tp.inv_q1);
         if (p1 > tp.cap1) p1 = tp.cap1;
         ts += p1 * tp.w1;
     }
