@@ -399,8 +399,9 @@ constexpr uint32_t PROP_STATS_HOPS = 65;  // GSX_MAX_HOPS + 1
 hipError_t launch_prop_stats(const PropState& ps, uint32_t* msg_hop_hist, uint32_t* node_received,
                              unsigned long long* node_hop_sum, hipStream_t st);
 // gsx_score_stats (gsx_score_stats.hip): the selected pairs per score bin
-// (bin(s) = the edges k with s >= edges[k]) for the engine, per observer row
-// and per peer, and the lowest selected score per row and per peer.  Any
+// (bin(s) = the edges k with !(s < edges[k]): a NaN in the top bin) for the
+// engine, per observer row and per peer, and the lowest selected score that
+// is no NaN per row and per peer.  Any
 // output may be null.  The counters are added to (the caller zeroes them); the
 // minima are held as order-preserving u64 keys of the doubles during the
 // pass: launch_score_stats_fill presets +inf, launch_score_stats_unkey leaves

@@ -41,7 +41,11 @@ namespace gsx {
 // whose decision byte is AcceptControl has FWD_GIN too: pubsub.go:1019-1023
 // strips the payload of such an RPC, with the same consequences for messages.
 // So FWD_GIN = "u accepts no message from v": score < graylist OR throttled;
-// a pair without it is at or above the graylist threshold.
+// a pair without it is not below the graylist threshold: at or above it, or
+// its score is a NaN (`NaN < graylist` is false in the reference too, which
+// accepts such a peer; `score >= publishThreshold` below refuses it).  A NaN
+// that comes from the pair's own terms (P5 to P7) stays one under every credit,
+// so no byte of such a pair depends on its credits.
 // Floodsub and RandomSub accept all.
 // The score is the one of the call start, like the publishThreshold tests.
 __device__ __forceinline__ uint8_t fwd_byte(const PropState& ps, const DevState& s, uint64_t r) {
@@ -2103,8 +2107,10 @@ __global__ __launch_bounds__(256) void k_prop_defer(PropState ps, DevState s, De
         // gossipsub edge's own threshold is AcceptFrom's (FWD_GIN holds for every
         // pair with score < graylist on the cached scores — and for the pairs the
         // gater throttles, which take no credits either — and such pairs are
-        // skipped; a pair without it is at or above graylist), so its score is
-        // never read — most of the pass's bytes on a gossipsub overlay
+        // skipped; a pair without it is at or above graylist, or its score is a
+        // NaN of its own terms P5 to P7, which no credit changes: its sums may
+        // wait as well), so its score is never read — most of the pass's bytes
+        // on a gossipsub overlay
 #pragma unroll
         for (int i = 0; i < DU; ++i) {
             const uint64_t q = q0 + i * stride;

@@ -90,9 +90,12 @@ __global__ __launch_bounds__(SS_THREADS) void k_score_stats(ScoreStatsArgs a) {
         unsigned long long key = KEY_INF;
         if (sel) {
             const double s = a.score[p];
+            // the edges the score is not below: a NaN is below none (the router's `score < threshold`
+            // is false for it) and lands in the top bin
 #pragma unroll
-            for (uint32_t k = 0; k < SS_MAX_EDGES; ++k) bin += (k < a.n_edges && s >= a.edges[k]) ? 1u : 0u;
-            key = score_key(s);
+            for (uint32_t k = 0; k < SS_MAX_EDGES; ++k) bin += (k < a.n_edges && !(s < a.edges[k])) ? 1u : 0u;
+            // the minima skip a NaN: its key would sort by its sign bit, below -inf or above +inf
+            if (s == s) key = score_key(s);
         }
 
         // the run of lanes that share this lane's observer: [first lane with `head`, end]

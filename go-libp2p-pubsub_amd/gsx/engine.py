@@ -120,9 +120,11 @@ class PropStats:
 
 class ScoreStats:
     """Threshold standings of the scores (gsx_score_stats): the selected pairs
-    per score bin, bin(s) = the edges k with s >= edges[k], as hist [B] u64 for
+    per score bin, bin(s) = the edges k with not s < edges[k] (a NaN score: the
+    top bin, it is below no edge), as hist [B] u64 for
     the engine, obs_bins [n_local, B] u32 per observer row with obs_min
-    [n_local] f64 (the row's lowest selected score, +inf if none), peer_bins
+    [n_local] f64 (the row's lowest selected score that is no NaN, +inf if
+    none), peer_bins
     [n_total, B] u32 per peer with peer_min [n_total] f64; B = len(edges) + 1.
     Any of them may be None.  Everything below is numpy on those tables."""
 

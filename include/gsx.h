@@ -334,9 +334,17 @@ int gsx_export_state(gsx_engine* e, gsx_state_view* s);
  * router graylists, its mesh degree) and per peer (how many observers
  * graylist a node).
  *
- * bin(s) = the number of k with s >= edges[k], 0 .. n_edges: a score exactly
+ * bin(s) = the number of k with !(s < edges[k]), 0 .. n_edges: a score exactly
  * on an edge falls in the upper bin (the reference's gates are all
- * score < threshold).  With n_edges == 0 every selected pair is in bin 0:
+ * score < threshold).
+ * Non-finite scores (gsx_set_app_scores and gsx_import_state take any double):
+ * -inf and +inf bin and minimise as the ordered values they are.  A NaN score
+ * is below no edge, as the router's `score < threshold` is false for it: a
+ * selected pair with a NaN score counts in the top bin, n_edges, so that the
+ * pairs below an edge are the pairs the router's gate refuses.  The minima
+ * ignore NaN scores: obs_min / peer_min are the minimum of the selected scores
+ * that are not NaN, +inf if there is none, and never NaN themselves.
+ * With n_edges == 0 every selected pair is in bin 0:
  * obs_bins[u] is then row u's selected pairs — under GSX_SS_MESH the node's
  * mesh degree on spec.topic. */
 #define GSX_SS_MAX_EDGES 7

@@ -37,9 +37,9 @@ def reference(scores, pair_flags, rec_flags, row_ptr, col, n_total, edges, selec
     peer_bins = np.zeros((n_total, B), dtype=np.uint32)
     np.add.at(peer_bins, (col[q], b), np.uint32(1))
     obs_min = np.full(n_local, np.inf)
-    np.minimum.at(obs_min, obs[q], scores[q])
+    np.fmin.at(obs_min, obs[q], scores[q])  # (fmin: the minima ignore a NaN score, gsx.h)
     peer_min = np.full(n_total, np.inf)
-    np.minimum.at(peer_min, col[q], scores[q])
+    np.fmin.at(peer_min, col[q], scores[q])
     return {"hist": hist, "obs_bins": obs_bins, "obs_min": obs_min, "peer_bins": peer_bins, "peer_min": peer_min}
 
 
