@@ -90,10 +90,26 @@ __host__ __device__ __forceinline__ size_t zmap_bytes(uint64_t n_tiles, uint32_t
     return ((n_tiles * n_topics * 2 + 3) / 4 + 1) * 4;
 }
 
+// Pair zero map, the per-pair counterpart (most peers have no application
+// score, most IPs are not shared beyond the threshold):
+//   pzmap [p/64][4]             u8 per tile: PZ_APP, PZ_P6, two spare
+// PZ_APP == ZM_ZERO: app[p] is bitwise +0.0 for every pair of the tile.
+// PZ_P6 == ZM_ZERO: ip_colocation(s, pp, p) is +0.0 for every present pair of
+// the tile, under the current ipg, ipcount, threshold and whitelist bits.
+// ZM_MAYBE says nothing; app, ipg and ipcount stay the only source of truth.
+// The same discipline: whatever may break an entry marks it first (pzmap_mark,
+// pzmap_mark_row, gsx_ops.h; the host's bulk paths mark the whole map), and
+// only the refresh pass clears one, when all 64 pairs of the tile are present
+// and it saw +0.0 in each.  A fresh map is all ZM_MAYBE.  The 4-byte entry is
+// one aligned 32-bit scalar load per wave.
+constexpr int PZ_APP = 0, PZ_P6 = 1, PZ_ENTRY = 4;
+__host__ __device__ __forceinline__ size_t pzmap_bytes(uint64_t n_tiles) { return (n_tiles + 1) * PZ_ENTRY; }
+
 struct DevState {
     double* rec;          // tiled records (GRAFT slot holds int64 bits)
     uint8_t* rflags;      // tiled record flags
     uint8_t* zmap;        // per (tile, topic, MFP | IMD): ZM_ZERO / ZM_MAYBE
+    uint8_t* pzmap;       // per (tile, PZ_APP | PZ_P6): ZM_ZERO / ZM_MAYBE
     uint8_t* pflags;      // per pair: PRESENT | CONNECTED
     int64_t* expire;      // per pair: retention expiry
     double* bp;           // per pair: behaviourPenalty
@@ -1022,6 +1038,7 @@ hipError_t launch_refresh_score(const DevState& s, const KernParams& kp, int64_t
 struct DevIpMove {
     uint64_t pair;
     uint32_t g0, g1;  // the pair's new (observer, IP) groups, IPG_WL flagged, IPG_NONE for none
+    uint64_t row_lo, row_hi;  // the observer's pairs: the tiles whose PZ_P6 entry the move marks
 };
 hipError_t launch_set_ips(const DevState& s, const DevIpMove* mv, const uint32_t* group_off, uint32_t n_groups,
                           hipStream_t st);
@@ -1063,4 +1080,13 @@ hipError_t launch_mesh_time_import(const DevState& s, const int64_t* topic_major
 hipError_t launch_zmap_check(const DevState& s, uint32_t* n_bad, hipStream_t st);
 // Counts into *n_marked the zero-map entries that say ZM_MAYBE.
 hipError_t launch_zmap_marked(const DevState& s, uint32_t* n_marked, hipStream_t st);
+// The pair zero map.  fill: byte `which` (PZ_*) of every entry = val.
+// mark_app: PZ_APP of every tile holding an app score that is not bitwise +0.0.
+// check: the entries that say ZM_ZERO while a pair of the tile holds such an
+// app score (PZ_APP) or a present pair a non-zero ip_colocation (PZ_P6), added
+// to *n_bad (always 0: a check).  marked: the entries whose byte says ZM_MAYBE.
+hipError_t launch_pzmap_fill(const DevState& s, int which, uint8_t val, hipStream_t st);
+hipError_t launch_pzmap_mark_app(const DevState& s, hipStream_t st);
+hipError_t launch_pzmap_check(const DevState& s, const DevPeerParams& pp, uint32_t* n_bad, hipStream_t st);
+hipError_t launch_pzmap_marked(const DevState& s, int which, uint32_t* n_marked, hipStream_t st);
 }  // namespace gsx

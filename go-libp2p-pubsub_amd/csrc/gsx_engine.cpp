@@ -97,6 +97,7 @@ struct gsx_engine {
     double* d_rec = nullptr;      // tiled records, gsx_device.h
     uint8_t* d_rflags = nullptr;  // tiled record flags
     uint8_t* d_zmap = nullptr;    // zero map of MFP / IMD per (tile, topic), gsx_device.h
+    uint8_t* d_pzmap = nullptr;   // pair zero map of app / P6 per tile, gsx_device.h
     void* d_tmp = nullptr;        // import/export staging of one topic-major field
     uint32_t* d_nbad = nullptr;
     uint8_t *d_pflags = nullptr, *d_eflags = nullptr;
@@ -623,6 +624,7 @@ gsx::DevState dev_state(const gsx_engine* e) {
     s.rec = e->d_rec;
     s.rflags = e->d_rflags;
     s.zmap = e->d_zmap;
+    s.pzmap = e->d_pzmap;
     s.pflags = e->d_pflags;
     s.expire = e->d_expire;
     s.bp = e->d_bp;
@@ -638,6 +640,24 @@ gsx::DevState dev_state(const gsx_engine* e) {
     s.wb_period = e->wb_period;
     s.decay_to_zero = e->pp.decay_to_zero;
     return s;
+}
+
+// PZ_P6 of the whole pair zero map marked: with any bulk change of what
+// ip_colocation reads (IP lists, counts, present bits, whitelist, threshold).
+int pzmap_mark_p6(gsx_engine* e) {
+    if (!e->loaded) return GSX_OK;
+    HIPCHK(e, gsx::launch_pzmap_fill(dev_state(e), gsx::PZ_P6, gsx::ZM_MAYBE, e->stream));
+    return GSX_OK;
+}
+
+// The device's copy of a queued event.  AddPeer uses neither now_ns nor arg:
+// they carry the observer's row bounds (ev_add_peer's PZ_P6 mark, gsx_ops.h).
+gsx::DevEvent dev_event(const gsx_engine* e, const gsx_event& x) {
+    if (x.kind == GSX_EV_ADD_PEER) {
+        const uint32_t u = e->pair_obs[x.pair];
+        return gsx::DevEvent{x.kind, x.topic, x.pair, e->row_ptr[u], e->row_ptr[u + 1]};
+    }
+    return gsx::DevEvent{x.kind, x.topic, x.pair, x.now_ns, x.arg};
 }
 
 // Every record's pending decays applied and stored, the phase restarted: before
@@ -927,11 +947,12 @@ void free_state(gsx_engine* e) {
     gx_abort(e);
     void* ptrs[] = {e->d_rec,    e->d_rflags, e->d_tmp, e->d_nbad,    e->d_pflags, e->d_eflags,
                     e->d_expire, e->d_bp,     e->d_app, e->d_score,   e->d_ipg,    e->d_ipcount,
-                    e->d_col,    e->d_zmap};
+                    e->d_col,    e->d_zmap,   e->d_pzmap};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     e->d_rec = nullptr;
     e->d_zmap = nullptr;
+    e->d_pzmap = nullptr;
     e->d_tmp = nullptr;
     e->d_nbad = nullptr;
     e->d_rflags = e->d_pflags = e->d_eflags = nullptr;
@@ -1283,7 +1304,7 @@ int flush(gsx_engine* e) {
     auto* hev = static_cast<gsx::DevEvent*>(e->h_stage);
     for (size_t i = 0; i < n; ++i) {
         const gsx_event& s = e->pending[order[i]];
-        hev[i] = gsx::DevEvent{s.kind, s.topic, s.pair, s.now_ns, s.arg};
+        hev[i] = dev_event(e, s);
     }
     std::memcpy(static_cast<char*>(e->h_stage) + ev_bytes, group_off.data(), off_bytes);
     HIPCHK(e, hipMemcpyAsync(e->d_stage, e->h_stage, total, hipMemcpyHostToDevice, e->stream));
@@ -1643,6 +1664,9 @@ int gsx_set_peer_params(gsx_engine* e, const gsx_peer_score_params* p) {
     int rc = flush(e);  // queued events see the params they were issued under
     if (rc) return rc;
     if ((rc = materialize_all(e))) return rc;  // (DecayToZero of the pending decays)
+    if (p->ip_colocation_factor_threshold != e->pp.ip_colocation_factor_threshold ||
+        std::memcmp(&p->ip_colocation_factor_weight, &e->pp.ip_colocation_factor_weight, sizeof(double)) != 0)
+        if ((rc = pzmap_mark_p6(e))) return rc;  // the map's P6 entries speak of the old threshold
     e->pp = *p;
     e->pp_set = true;
     e->invalidate_scores();
@@ -1803,6 +1827,7 @@ int load_overlay(gsx_engine* e, uint32_t n_total, uint32_t node_lo, uint32_t n_n
     int rc = 0;
     if ((rc = dalloc(e, &e->d_rec, R * gsx::NFIELD)) || (rc = dalloc(e, &e->d_rflags, R)) ||
         (rc = dalloc(e, &e->d_zmap, gsx::zmap_bytes(e->n_tiles, e->T))) ||
+        (rc = dalloc(e, &e->d_pzmap, gsx::pzmap_bytes(e->n_tiles))) ||
         (rc = dalloc(e, &e->d_nbad, 1)) || (rc = dalloc(e, &e->d_pflags, e->rs)) ||
         (rc = dalloc(e, &e->d_eflags, e->rs)) || (rc = dalloc(e, &e->d_expire, e->rs)) ||
         (rc = dalloc(e, &e->d_bp, e->rs)) || (rc = dalloc(e, &e->d_app, e->rs)) ||
@@ -1817,6 +1842,8 @@ int load_overlay(gsx_engine* e, uint32_t n_total, uint32_t node_lo, uint32_t n_n
     HIPCHK(e, hipMemsetAsync(e->d_rflags, 0, R, e->stream));
     // every record is +0.0: the zero map says so everywhere (ZM_ZERO == 0)
     HIPCHK(e, hipMemsetAsync(e->d_zmap, gsx::ZM_ZERO, gsx::zmap_bytes(e->n_tiles, e->T), e->stream));
+    // the pair zero map starts out saying nothing: the first refresh clears what it finds zero
+    HIPCHK(e, hipMemsetAsync(e->d_pzmap, gsx::ZM_MAYBE, gsx::pzmap_bytes(e->n_tiles), e->stream));
     HIPCHK(e, hipMemsetAsync(e->d_pflags, 0, e->rs, e->stream));
     HIPCHK(e, hipMemsetAsync(e->d_expire, 0, sizeof(int64_t) * e->rs, e->stream));
     HIPCHK(e, hipMemsetAsync(e->d_bp, 0, sizeof(double) * e->rs, e->stream));
@@ -2048,6 +2075,7 @@ int gsx_set_ip_whitelist(gsx_engine* e, const uint32_t* ip_ids, size_t n) {
     e->state_changed();
     if (!e->loaded) return GSX_OK;
     HIPCHK(e, hipStreamSynchronize(e->stream));
+    if ((rc = pzmap_mark_p6(e))) return rc;  // a group that leaves the whitelist may be over the threshold
     return upload_ipg(e);
 }
 
@@ -2058,6 +2086,7 @@ int gsx_set_app_scores(gsx_engine* e, const double* app, size_t n) {
     int rc = flush(e);  // a queued RemovePeer must see the app score it was issued under
     if (rc) return rc;
     HIPCHK(e, hipMemcpyAsync(e->d_app, app, sizeof(double) * n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, gsx::launch_pzmap_mark_app(dev_state(e), e->stream));  // (a tile now all zero is cleared by a refresh)
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->invalidate_scores();
     e->state_changed();
@@ -2098,7 +2127,7 @@ int gsx_set_pair_ips(gsx_engine* e, const uint64_t* pairs, const uint32_t* ips, 
             e->ipg_host[2 * (size_t)p + k] = g[k];
             if (g[k] != gsx::IPG_NONE && ips[2 * i + k] < e->ip_wl.size() && e->ip_wl[ips[2 * i + k]]) g[k] |= gsx::IPG_WL;
         }
-        mv[i] = gsx::DevIpMove{p, g[0], g[1]};
+        mv[i] = gsx::DevIpMove{p, g[0], g[1], (uint64_t)e->row_ptr[u], (uint64_t)e->row_ptr[u + 1]};
     }
     if (e->n_groups > groups0) {  // new keys: a longer count array, the old counts kept
         uint32_t* nc = nullptr;
@@ -2410,7 +2439,7 @@ int dropin_fast(gsx_engine* e) {
     auto* hev = reinterpret_cast<gsx::DevEvent*>(hb + ev_off);
     for (size_t i = 0; i < n; ++i) {
         const gsx_event& x = e->pending[order[i]];
-        hev[i] = gsx::DevEvent{x.kind, x.topic, x.pair, x.now_ns, x.arg};
+        hev[i] = dev_event(e, x);
     }
     std::memcpy(hb + go_off, goff.data(), go_b);
     if (!rows.empty()) std::memcpy(hb + ob_off, rows.data(), 4 * rows.size());
@@ -2572,6 +2601,7 @@ int gsx_import_state(gsx_engine* e, const gsx_state_view* s) {
     HIPCHK(e, hipMemcpyAsync(e->d_pflags, s->pair_flags, E, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipMemcpyAsync(e->d_expire, s->expire_ns, 8 * E, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipMemcpyAsync(e->d_bp, s->behaviour_penalty, 8 * E, hipMemcpyHostToDevice, e->stream));
+    if (int rc = pzmap_mark_p6(e)) return rc;  // new present bits, new counts
     HIPCHK(e, gsx::launch_rebuild_ipcount(ds, e->n_groups, e->stream));
     uint32_t n_bad = 0;
     HIPCHK(e, hipMemcpyAsync(&n_bad, e->d_nbad, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
@@ -2608,6 +2638,7 @@ int gsx_synthesize_state(gsx_engine* e, const gsx_synth_spec* sp) {
     e->phase = 0;                  // (every record and flag byte is overwritten)
     const gsx::DevState s = dev_state(e);
     HIPCHK(e, gsx::launch_synthesize(s, e->d_col, d, e->stream));
+    if (int rc = pzmap_mark_p6(e)) return rc;  // new present bits, new counts
     HIPCHK(e, gsx::launch_rebuild_ipcount(s, e->n_groups, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     e->invalidate_scores();
@@ -2671,6 +2702,33 @@ static int zero_map_count(gsx_engine* e, uint64_t* n, bool marked) {
 
 int gsx_zero_map_violations(gsx_engine* e, uint64_t* n) { return zero_map_count(e, n, false); }
 int gsx_zero_map_marked(gsx_engine* e, uint64_t* n) { return zero_map_count(e, n, true); }
+
+// The pair zero map's counts: which < 0 the entries that break its invariant,
+// else the entries whose byte `which` says "maybe non-zero".
+static int pair_zero_map_count(gsx_engine* e, uint64_t* n, int which) {
+    if (!e || !n) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    if (int rc = fold_deferred(e)) return rc;
+    if (int rc = flush(e)) return rc;
+    uint32_t n_bad = 0;
+    HIPCHK(e, hipMemsetAsync(e->d_nbad, 0, sizeof(uint32_t), e->stream));
+    if (which < 0) {
+        HIPCHK(e, gsx::launch_pzmap_check(dev_state(e), dev_peer_params(e), e->d_nbad, e->stream));
+    } else {
+        HIPCHK(e, gsx::launch_pzmap_marked(dev_state(e), which, e->d_nbad, e->stream));
+    }
+    HIPCHK(e, hipMemcpyAsync(&n_bad, e->d_nbad, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    *n = n_bad;
+    return GSX_OK;
+}
+
+int gsx_pair_zero_map_violations(gsx_engine* e, uint64_t* n) { return pair_zero_map_count(e, n, -1); }
+int gsx_pair_zero_map_marked(gsx_engine* e, uint32_t which, uint64_t* n) {
+    if (which != GSX_PZ_APP && which != GSX_PZ_P6) return GSX_EINVAL;
+    return pair_zero_map_count(e, n, (int)which);
+}
 
 // inspectScoresExtended, score.go:463-493
 int gsx_peer_score_snapshot(gsx_engine* e, gsx_score_snapshot* s) {

@@ -54,18 +54,28 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
     // not loaded, its value is the constant +0.0 and the arithmetic below is
     // unchanged (decay(0) = 0 is not written back, 0 * 0 * w4 adds the same
     // zero).  The record loads wait on nothing else.
-    const uint64_t zoff = wave_uniform(p / TILE) * (uint64_t)T * 2;
+    const uint64_t wtile = wave_uniform(p / TILE);
+    const uint64_t zoff = wtile * (uint64_t)T * 2;
     uint32_t zm[TT > 0 ? TT : 1];
     if constexpr (TT > 0) {
 #pragma unroll
         for (int t = 0; t < TT; ++t) zm[t] = zmap_pair(s.zmap, zoff + 2 * t);
     }
+    // The tile's pair zero map entry, one aligned 32-bit scalar load beside
+    // them: an application score or an IP colocation factor the entry says is
+    // zero is not loaded, its value is the constant +0.0 and its product is
+    // added as always.  A masked score pass takes only PZ_APP from it.
+    const uint32_t pz = __builtin_amdgcn_readfirstlane(reinterpret_cast<const uint32_t*>(s.pzmap)[wtile]);
+    const bool app_maybe = (pz >> (8 * PZ_APP)) & 0xFFu;
+    const bool p6_maybe = !REFRESH || ((pz >> (8 * PZ_P6)) & 0xFFu);
     const uint8_t st = s.pflags[p];
     if (!(st & PAIR_PRESENT)) {  // no peerStats: Score() returns 0 (:259-262)
         s.score[p] = 0.0;
         return;
     }
     const DevPeerParams& pp = kp.pp;
+    double p5 = 0.0;
+    if (app_maybe) p5 = s.app[p];  // early, with the record loads
     // Disconnected (retained) peers are not decayed (:503-516).
     const bool conn = REFRESH && (st & PAIR_CONNECTED);
     // Deferred write-back (REC_EPOCH, gsx_device.h): the decayed counters are
@@ -201,7 +211,24 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
         bp = decay(bp, pp.d7, pp.decay_to_zero);
         s.bp[p] = bp;
     }
-    s.score[p] = score_tail(s, pp, p, score, bp);
+    // score_tail (gsx_ops.h) behind the pair zero map.  Both tests are the
+    // wave's (pz is scalar): a tile whose entry says zero gathers nothing.
+    double p6 = 0.0;
+    const bool p6_read = pp.w6 != 0.0 && p6_maybe;
+    if (p6_read) p6 = ip_colocation(s, pp, p);
+    s.score[p] = score_tail_vals(pp, score, p5, p6, bp);
+    if constexpr (REFRESH) {
+        // A marked entry whose 64 pairs are all present (no lane returned
+        // above) and all hold +0.0: one lane clears it.  A tile with an absent
+        // pair, and the tail tile, keep their marks.
+        if ((app_maybe || p6_read) && __ballot(1) == ~0ull) {
+            uint8_t* const pzb = s.pzmap + wtile * PZ_ENTRY;
+            const bool z5 = app_maybe && __ballot(__double_as_longlong(p5) != 0) == 0;
+            const bool z6 = p6_read && __ballot(__double_as_longlong(p6) != 0) == 0;
+            if (z5 && lane == 0) pzb[PZ_APP] = ZM_ZERO;
+            if (z6 && lane == 0) pzb[PZ_P6] = ZM_ZERO;
+        }
+    }
 }
 
 // refreshScores' purge of expired retained peers (score.go:503-515).  Runs
@@ -225,7 +252,8 @@ __global__ __launch_bounds__(256) void k_purge(DevState s, int64_t now) {
 // the caller issued them.
 __device__ __forceinline__ void apply_event(const DevState& s, const DevPeerParams& pp, const DevEvent& e) {
     switch (e.kind) {
-    case 1: ev_add_peer(s, e.pair); break;
+    // AddPeer uses neither field: the host passes the observer's row bounds in them
+    case 1: ev_add_peer(s, pp, e.pair, (uint64_t)e.now_ns, (uint64_t)e.arg); break;
     case 2: ev_remove_peer(s, pp, e.pair, e.now_ns); break;
     case 3: ev_graft(s, e.pair, e.topic, e.now_ns); break;
     case 4: ev_prune(s, e.pair, e.topic); break;
@@ -233,7 +261,10 @@ __device__ __forceinline__ void apply_event(const DevState& s, const DevPeerPara
     case 6: ev_mesh(s, e.pair, e.topic); break;
     case 7: ev_invalid(s, e.pair, e.topic); break;
     case 8: ev_penalty(s, e.pair, e.arg); break;
-    case 9: s.app[e.pair] = __longlong_as_double((long long)e.arg); break;  // AppSpecificScore(p), :320
+    case 9:  // AppSpecificScore(p), :320
+        if (e.arg != 0) pzmap_mark(s, e.pair, PZ_APP);
+        s.app[e.pair] = __longlong_as_double((long long)e.arg);
+        break;
     default: break;
     }
 }
@@ -391,6 +422,42 @@ __global__ __launch_bounds__(256) void k_zmap_marked(DevState s, uint32_t* n_mar
     if (b && threadIdx.x % 64 == 0) atomicAdd(n_marked, (uint32_t)__popcll(b));
 }
 
+// ---- the pair zero map (gsx_device.h): bulk marks and checks -------------------
+
+__global__ __launch_bounds__(256) void k_pzmap_fill(DevState s, int which, uint8_t val) {
+    const uint64_t tile = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (tile < (s.n_pairs + TILE - 1) / TILE) s.pzmap[tile * PZ_ENTRY + which] = val;
+}
+
+// After a bulk store of app: any bit pattern but +0.0 marks its tile (-0.0 too).
+__global__ __launch_bounds__(256) void k_pzmap_mark_app(DevState s) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const bool nz = p < s.n_pairs && __double_as_longlong(s.app[p]) != 0;
+    if (__ballot(nz) != 0 && threadIdx.x % TILE == 0) s.pzmap[(p / TILE) * PZ_ENTRY + PZ_APP] = ZM_MAYBE;
+}
+
+// One wave per tile: an entry that says zero while a pair of the tile holds an
+// app score that is not +0.0 (present or not: an AddPeer does not mark), or a
+// present pair a non-zero IP colocation factor, counts.
+__global__ __launch_bounds__(256) void k_pzmap_check(DevState s, DevPeerParams pp, uint32_t* n_bad) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    bool bad5 = false, bad6 = false;
+    if (p < s.n_pairs) {
+        const uint8_t* const pzb = s.pzmap + (p / TILE) * PZ_ENTRY;
+        bad5 = pzb[PZ_APP] == ZM_ZERO && __double_as_longlong(s.app[p]) != 0;
+        bad6 = pzb[PZ_P6] == ZM_ZERO && (s.pflags[p] & PAIR_PRESENT) &&
+               __double_as_longlong(ip_colocation(s, pp, p)) != 0;
+    }
+    const uint32_t n = (__ballot(bad5) != 0) + (__ballot(bad6) != 0);
+    if (n && threadIdx.x % TILE == 0) atomicAdd(n_bad, n);
+}
+
+__global__ __launch_bounds__(256) void k_pzmap_marked(DevState s, int which, uint32_t* n_marked) {
+    const uint64_t tile = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t b = __ballot(tile < (s.n_pairs + TILE - 1) / TILE && s.pzmap[tile * PZ_ENTRY + which] != ZM_ZERO);
+    if (b && threadIdx.x % 64 == 0) atomicAdd(n_marked, (uint32_t)__popcll(b));
+}
+
 // ---- seeded synthetic state (gsx/synth.py restated on the device) ------------
 
 __device__ __forceinline__ double unif(uint64_t seed, uint64_t tag, uint64_t a, uint64_t b) {
@@ -478,6 +545,10 @@ __global__ __launch_bounds__(64) void k_set_ips(DevState s, const DevIpMove* __r
     for (uint32_t i = group_off[g]; i < group_off[g + 1]; ++i) {
         const uint64_t p = mv[i].pair;
         const bool present = s.pflags[p] & PAIR_PRESENT;
+        if (present) {  // the row's P6 may move: marked whole, whatever the new counts are
+            pzmap_mark(s, p, PZ_P6);
+            pzmap_mark_row(s, mv[i].row_lo, mv[i].row_hi);
+        }
         if (present) ipcount_add(s, p, -1);
         reinterpret_cast<uint2*>(const_cast<uint32_t*>(s.ipg))[p] = make_uint2(mv[i].g0, mv[i].g1);
         if (present) ipcount_add(s, p, +1);
@@ -614,6 +685,32 @@ hipError_t launch_zmap_marked(const DevState& s, uint32_t* n_marked, hipStream_t
     if (s.n_pairs == 0) return hipSuccess;
     const uint64_t n = (s.n_pairs + TILE - 1) / TILE * s.n_topics * 2;
     hipLaunchKernelGGL(k_zmap_marked, dim3(blocks_for(n, 256)), dim3(256), 0, st, s, n_marked);
+    return hipGetLastError();
+}
+
+hipError_t launch_pzmap_fill(const DevState& s, int which, uint8_t val, hipStream_t st) {
+    if (s.n_pairs == 0) return hipSuccess;
+    const uint64_t n_tiles = (s.n_pairs + TILE - 1) / TILE;
+    hipLaunchKernelGGL(k_pzmap_fill, dim3(blocks_for(n_tiles, 256)), dim3(256), 0, st, s, which, val);
+    return hipGetLastError();
+}
+
+hipError_t launch_pzmap_mark_app(const DevState& s, hipStream_t st) {
+    if (s.n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pzmap_mark_app, dim3(blocks_for(s.n_pairs, 256)), dim3(256), 0, st, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_pzmap_check(const DevState& s, const DevPeerParams& pp, uint32_t* n_bad, hipStream_t st) {
+    if (s.n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pzmap_check, dim3(blocks_for(s.n_pairs, 256)), dim3(256), 0, st, s, pp, n_bad);
+    return hipGetLastError();
+}
+
+hipError_t launch_pzmap_marked(const DevState& s, int which, uint32_t* n_marked, hipStream_t st) {
+    if (s.n_pairs == 0) return hipSuccess;
+    const uint64_t n_tiles = (s.n_pairs + TILE - 1) / TILE;
+    hipLaunchKernelGGL(k_pzmap_marked, dim3(blocks_for(n_tiles, 256)), dim3(256), 0, st, s, which, n_marked);
     return hipGetLastError();
 }
 

@@ -29,22 +29,28 @@ __device__ __forceinline__ double ip_colocation(const DevState& s, const DevPeer
 }
 
 // The per-pair tail of score(): topic cap, P5, P6, P7 (score.go:315-332).
-__device__ __forceinline__ double score_tail(const DevState& s, const DevPeerParams& pp, uint64_t p, double score,
-                                             double bp) {
+// From p5 and p6 as given (p6 is not read when w6 == 0): the refresh pass passes
+// the constant +0.0 for what the pair zero map says is zero, and every product
+// is still executed.
+__device__ __forceinline__ double score_tail_vals(const DevPeerParams& pp, double score, double p5, double p6,
+                                                  double bp) {
     if (pp.topic_score_cap > 0 && score > pp.topic_score_cap) score = pp.topic_score_cap;
-    const double p5 = s.app[p];
     score += p5 * pp.w5;
-    // With w6 == 0 the term is +-0 and score (never -0) is unchanged: skip the gather.
-    if (pp.w6 != 0.0) {
-        const double p6 = ip_colocation(s, pp, p);
-        score += p6 * pp.w6;
-    }
+    // With w6 == 0 the term is +-0 and score (never -0) is unchanged.
+    if (pp.w6 != 0.0) score += p6 * pp.w6;
     if (bp > pp.thr7) {
         const double excess = bp - pp.thr7;
         const double p7 = excess * excess;
         score += p7 * pp.w7;
     }
     return score;
+}
+__device__ __forceinline__ double score_tail(const DevState& s, const DevPeerParams& pp, uint64_t p, double score,
+                                             double bp) {
+    const double p5 = s.app[p];
+    // With w6 == 0 the term is not added: skip the gather.
+    const double p6 = pp.w6 != 0.0 ? ip_colocation(s, pp, p) : 0.0;
+    return score_tail_vals(pp, score, p5, p6, bp);
 }
 
 // ---- P1's Duration division (score.go:280) ------------------------------------
@@ -138,6 +144,18 @@ __device__ __forceinline__ double decay(double x, double d, double dtz) {
 // the constant: lanes racing on one tile's byte all write the same value.
 __device__ __forceinline__ void zmap_mark(const DevState& s, uint64_t p, uint32_t t, int field) {
     s.zmap[zmap_index(p, t, s.n_topics, field)] = ZM_MAYBE;
+}
+
+// The pair zero map's marks (gsx_device.h), as plain: one tile's entry, and
+// PZ_P6 of every tile the pairs [lo, hi) of one observer's row overlap (an
+// (observer, IP) group's pairs all lie in that row, in any of its tiles).
+__device__ __forceinline__ void pzmap_mark(const DevState& s, uint64_t p, int which) {
+    s.pzmap[(p / TILE) * PZ_ENTRY + which] = ZM_MAYBE;
+}
+__device__ __forceinline__ void pzmap_mark_row(const DevState& s, uint64_t lo, uint64_t hi) {
+    if (hi > s.n_pairs) hi = s.n_pairs;
+    if (lo >= hi) return;
+    for (uint64_t tile = lo / TILE; tile <= (hi - 1) / TILE; ++tile) s.pzmap[tile * PZ_ENTRY + PZ_P6] = ZM_MAYBE;
 }
 
 // ---- deferred write-back of the decayed counters (REC_EPOCH, gsx_device.h) ----
@@ -276,7 +294,9 @@ __device__ __forceinline__ bool scored_topic(const DevState& s, uint64_t p, uint
     return (s.pflags[p] & PAIR_PRESENT) && topic < s.n_topics && s.tp[topic].scored;
 }
 
-__device__ inline void ev_add_peer(const DevState& s, uint64_t p) {  // AddPeer :588-602
+// [row_lo, row_hi): the pairs of p's observer (the host's row bounds).
+__device__ inline void ev_add_peer(const DevState& s, const DevPeerParams& pp, uint64_t p, uint64_t row_lo,
+                                   uint64_t row_hi) {  // AddPeer :588-602
     const uint8_t st = s.pflags[p];
     const uint8_t ep = (uint8_t)(s.phase << REC_EPOCH_SHIFT);  // the records are current as of this phase
     if (!(st & PAIR_PRESENT)) {  // new peerStats{topics: {}}
@@ -288,6 +308,17 @@ __device__ inline void ev_add_peer(const DevState& s, uint64_t p) {  // AddPeer 
         s.bp[p] = 0.0;
         s.expire[p] = 0;
         ipcount_add(s, p, +1);  // setIPs
+        // A group that is now above the threshold gives every pair carrying it a
+        // P6, this one included: PZ_P6 of the whole row.  At or below it nothing
+        // changes (ordinary churn leaves the map alone); a whitelisted group
+        // never counts.
+        const uint2 g = reinterpret_cast<const uint2*>(s.ipg)[p];
+        const bool over_x = g.x != IPG_NONE && !(g.x & IPG_WL) && (int64_t)s.ipcount[g.x] > pp.thr6;
+        const bool over_y = g.y != IPG_NONE && !(g.y & IPG_WL) && (int64_t)s.ipcount[g.y] > pp.thr6;
+        if (over_x || over_y) {
+            pzmap_mark(s, p, PZ_P6);
+            pzmap_mark_row(s, row_lo, row_hi);
+        }
     } else if (!(st & PAIR_CONNECTED)) {  // a retained pair reconnects: it was not decayed meanwhile
         for (uint32_t t = 0; t < s.n_topics; ++t) {
             const size_t fi = flag_index(p, t, s.n_topics);

@@ -33,6 +33,8 @@ GSX_REC_IN_MESH = 0x01
 GSX_REC_ACTIVE = 0x02
 GSX_PAIR_PRESENT = 0x01
 GSX_PAIR_CONNECTED = 0x02
+GSX_PZ_APP = 0  # gsx_pair_zero_map_marked: the application-score entries
+GSX_PZ_P6 = 1  # ... the IP-colocation entries
 
 # gsx_event_kind
 EV_ADD_PEER = 1
@@ -529,6 +531,8 @@ SIGNATURES = {
     "gsx_export_state": (C.c_int, [C.c_void_p, P(StateView)]),
     "gsx_zero_map_violations": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
     "gsx_zero_map_marked": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
+    "gsx_pair_zero_map_violations": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
+    "gsx_pair_zero_map_marked": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint64)]),
     "gsx_set_decay_writeback": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_last_refresh_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "gsx_synthesize_state": (C.c_int, [C.c_void_p, P(SynthSpec)]),

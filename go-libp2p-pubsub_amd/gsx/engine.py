@@ -1051,3 +1051,16 @@ class Engine:
         n = C.c_uint64()
         self._chk(self.lib.gsx_zero_map_marked(self.h, C.byref(n)), "gsx_zero_map_marked")
         return n.value
+
+    def pair_zero_map_violations(self) -> int:
+        """gsx_pair_zero_map_violations: pair-zero-map entries that say zero over a non-zero
+        application score or IP colocation factor (always 0)."""
+        n = C.c_uint64()
+        self._chk(self.lib.gsx_pair_zero_map_violations(self.h, C.byref(n)), "gsx_pair_zero_map_violations")
+        return n.value
+
+    def pair_zero_map_marked(self, which: int) -> int:
+        """gsx_pair_zero_map_marked: tiles whose entry `which` (abi.GSX_PZ_APP, abi.GSX_PZ_P6) says "maybe non-zero"."""
+        n = C.c_uint64()
+        self._chk(self.lib.gsx_pair_zero_map_marked(self.h, which, C.byref(n)), "gsx_pair_zero_map_marked")
+        return n.value

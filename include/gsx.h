@@ -400,6 +400,22 @@ int gsx_zero_map_violations(gsx_engine* e, uint64_t* n);
  * a store of a non-zero penalty counter marks its tile's entry, a refresh that
  * finds the whole tile back at +0.0 clears it. */
 int gsx_zero_map_marked(gsx_engine* e, uint64_t* n);
+/* The pair zero map: per tile of 64 pairs, one entry for the application
+ * scores and one for the IP colocation factors (P6), which lets the refresh
+ * pass skip the loads of a tile where every one is +0.0.  *n = the entries that
+ * say zero while a pair of the tile holds an application score of another bit
+ * pattern, or a present pair a non-zero IP colocation factor.  Always 0; a
+ * test hook and a debugging aid. */
+int gsx_pair_zero_map_violations(gsx_engine* e, uint64_t* n);
+/* *n = the entries of one kind that say "maybe non-zero": all of them after a
+ * load.  A refresh clears the entry of a tile whose 64 pairs are all present
+ * and hold zero; a store of a non-zero application score marks its tile, an
+ * AddPeer that takes a non-whitelisted (observer, IP) group above
+ * IPColocationFactorThreshold marks the tiles of the observer's row, and bulk
+ * changes (IP lists, whitelist, threshold, imported state) mark every P6 entry. */
+#define GSX_PZ_APP 0u
+#define GSX_PZ_P6 1u
+int gsx_pair_zero_map_marked(gsx_engine* e, uint32_t which, uint64_t* n);
 /* How often gsx_refresh stores the decayed counters: every k-th refresh, k in
  * {1, 2, 4} (default 4).  A refresh's scores need the decayed values only in
  * registers; in between, a record's stored counters lag by up to k - 1 decays,
