@@ -1089,4 +1089,49 @@ hipError_t launch_pzmap_fill(const DevState& s, int which, uint8_t val, hipStrea
 hipError_t launch_pzmap_mark_app(const DevState& s, hipStream_t st);
 hipError_t launch_pzmap_check(const DevState& s, const DevPeerParams& pp, uint32_t* n_bad, hipStream_t st);
 hipError_t launch_pzmap_marked(const DevState& s, int which, uint32_t* n_marked, hipStream_t st);
+
+// ---- the tag tracer (gsx_tags.hip; tag_tracer.go) ---------------------------
+// One u8 delivery tag per (pair, topic), tiled like rflag ([p/64][t][64],
+// flag_index), so a wave reads a topic's tags of its 64 pairs as one 64-byte
+// span.  Protection is not stored: pubsub:<direct> is EDGE_DIRECT of a present
+// pair, pubsub:<topic> the record's REC_IN_MESH bit.
+struct TagState {
+    uint8_t* tags;            // [n_tiles][n_topics][64]
+    const uint8_t* rflags;    // tiled record flags (REC_IN_MESH)
+    const uint8_t* pflags;    // per pair: PRESENT | CONNECTED
+    const uint8_t* eflags;    // per pair: EDGE_*
+    const uint32_t* pair_obs; // per pair: its observer
+    const uint64_t* sub;      // [node] joined topics (null: every node joined every topic)
+    uint64_t n_pairs, n_tiles;
+    uint32_t n_topics, n_nodes;
+    uint32_t bump, decay_amount, cap;
+};
+struct DevTagEvent {  // keys are unique within a launch (the host merges equal ones)
+    uint64_t pair;
+    uint32_t topic;
+    uint32_t add;  // min(count * bump, cap)
+};
+constexpr uint8_t CONN_DIRECT = 0x01, CONN_MESH = 0x02;  // gsx_conn_values' protect bits
+// gsx_conn_trim's per-pair key: the pair's value (<= 64 x 255) if it is in C and
+// unprotected, CONN_KEY_PROT if in C and protected, CONN_KEY_OUT if not in C.
+constexpr uint32_t CONN_KEY_PROT = 0xFFFFFFFEu, CONN_KEY_OUT = 0xFFFFFFFFu;
+constexpr uint32_t CONN_VALUE_MAX = 64u * 255u;
+constexpr uint32_t CONN_LONG_ROW = 4096;  // rows above it take one 1024-thread block each, the rest one wave each
+hipError_t launch_tag_events(const TagState& t, const DevTagEvent* ev, uint32_t n, hipStream_t st);
+// DecayFixed: every tag = max(0, tag - sub), sub <= 255
+hipError_t launch_tag_decay(const TagState& t, uint32_t sub, hipStream_t st);
+// Zeroes the tags of every (pair, topic) whose observer has not joined the topic.
+hipError_t launch_tag_clear_unjoined(const TagState& t, hipStream_t st);
+// gsx_tag_fold_prop: acc [W] the ACCEPT messages; dup_rows k_prop_dup_rows' output;
+// near != 0 counts the same-hop duplicates too.
+hipError_t launch_tag_fold(const TagState& t, const PropState& ps, const uint64_t* dup_rows, const uint64_t* acc,
+                           uint32_t near, hipStream_t st);
+// topic-major export [t * n_pairs + p]
+hipError_t launch_tag_export(const TagState& t, uint8_t* out, hipStream_t st);
+// value / protect may each be null; key (null or [n_pairs]) is gsx_conn_trim's
+hipError_t launch_conn_values(const TagState& t, uint32_t* value, uint8_t* protect, uint32_t* key, hipStream_t st);
+// long_rows: the n_long rows above CONN_LONG_ROW pairs (device list)
+hipError_t launch_conn_trim(const TagState& t, const int64_t* row_ptr, const uint32_t* key, uint32_t low_water,
+                            const uint32_t* long_rows, uint32_t n_long, uint8_t* trim, uint32_t* node_trimmed,
+                            hipStream_t st);
 }  // namespace gsx

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <map>
 #include <atomic>
 #include <chrono>
 #include <array>
@@ -458,6 +459,25 @@ struct gsx_engine {
     // bumped by every full gsx_accept_from and every gsx_gater_enforce: the fwd bytes of a
     // propagation are reused only under the decision set they were computed from (never reset)
     uint64_t gater_dec_gen = 0;
+
+    // the tag tracer (gsx_set_tag_params; gsx_tags.hip): the tag bytes, tiled like
+    // d_rflags, and the nearFirst map of tag_tracer.go:53-55 on the host
+    struct {
+        bool on = false;
+        gsx_tag_params p{};
+        uint8_t* tags = nullptr;       // [n_tiles][T][64]
+        void* ev = nullptr;            // gsx_tag_events' device staging (grown)
+        size_t ev_bytes = 0;
+        uint64_t* fold_buf = nullptr;  // gsx_tag_fold_prop: the duplicate rows [E][W], then the ACCEPT words [W] (grown)
+        size_t fold_cap = 0;
+        uint32_t* key = nullptr;       // [E] gsx_conn_trim's keys
+        uint32_t* long_rows = nullptr; // rows above CONN_LONG_ROW pairs
+        uint32_t n_long = 0;
+        // the device side of results that go to host memory (each sized once)
+        uint32_t *val_buf = nullptr, *nt_buf = nullptr;
+        uint8_t *prot_buf = nullptr, *trim_buf = nullptr, *exp_buf = nullptr;
+        std::map<std::pair<uint32_t, uint64_t>, std::vector<uint64_t>> near;  // (observer, msg_id) -> pairs
+    } tagt;
 
     // range sharding (gsx_load_overlay_shard / gsx_shard_*_plan)
     uint32_t n_total = 0, node_lo = 0;
@@ -939,6 +959,15 @@ void gater_free(gsx_engine* e) {
     ++e->gater_dec_gen;
 }
 
+// Frees the tag tracer: its tags, buffers and pending messages.
+void tag_free(gsx_engine* e) {
+    auto& G = e->tagt;
+    void* tp[] = {G.tags, G.ev, G.fold_buf, G.key, G.long_rows, G.val_buf, G.nt_buf, G.prot_buf, G.trim_buf, G.exp_buf};
+    for (void* p : tp)
+        if (p) (void)hipFree(p);
+    G = {};
+}
+
 void free_state(gsx_engine* e) {
     if (e->vc_stream) (void)hipStreamSynchronize(e->vc_stream);  // (code-plane builds in flight)
     e->vc_busy[0] = e->vc_busy[1] = false;
@@ -1002,6 +1031,7 @@ void free_state(gsx_engine* e) {
     e->prop.d_hop_flag = dhf;
     e->prop.hop_seq = hseq;
     gater_free(e);  // the gater belongs to the overlay it was set on
+    tag_free(e);    // and so does the tag tracer
     e->d_send_pair = e->d_pair_obs = e->d_halo_node = e->d_halo_pair = e->d_send_slot = nullptr;
     e->d_rmark_v = e->d_rmark_u = nullptr;
     e->d_send_dest = nullptr;
@@ -1152,6 +1182,26 @@ gsx::GaterState dev_gater(const gsx_engine* e) {
     g.retain_ns = G.p.retain_stats_ns;
     g.quiet_ns = G.p.quiet_ns;
     return g;
+}
+
+// ---- the tag tracer's state (gsx.h; kernels in gsx_tags.hip) -------------------
+gsx::TagState dev_tags(const gsx_engine* e) {
+    const auto& G = e->tagt;
+    gsx::TagState t{};
+    t.tags = G.tags;
+    t.rflags = e->d_rflags;
+    t.pflags = e->d_pflags;
+    t.eflags = e->d_eflags;
+    t.pair_obs = e->d_pair_obs;
+    t.sub = e->members_on ? e->d_sub : nullptr;
+    t.n_pairs = e->E;
+    t.n_tiles = e->n_tiles;
+    t.n_topics = e->T;
+    t.n_nodes = e->n_nodes;
+    t.bump = G.p.bump;
+    t.decay_amount = G.p.decay_amount;
+    t.cap = G.p.cap;
+    return t;
 }
 
 // The group arrays cover n_nodes "<unknown>" groups and every (observer, IP)
@@ -4556,6 +4606,310 @@ int gsx_gater_gate_pairs(gsx_engine* e, uint64_t* none, uint64_t* control) {
     return GSX_OK;
 }
 
+// ---- the tag tracer (tag_tracer.go) and connection trims -----------------------
+
+namespace {
+int tag_on(gsx_engine* e) {
+    if (!e->tagt.on) return fail(e, GSX_ESTATE, "no tag tracer (gsx_set_tag_params)");
+    return GSX_OK;
+}
+
+bool tag_joined(const gsx_engine* e, uint32_t u, uint32_t topic) {
+    return !e->members_on || ((e->h_sub[u] >> topic) & 1);
+}
+
+// gsx_timing_begin: the call's launches are one timed region
+struct TagRegion {
+    gsx_engine* e;
+    bool on;
+    explicit TagRegion(gsx_engine* e_) : e(e_), on(e_->t_active && e_->t_used < e_->t_max) {}
+    hipError_t begin() { return on ? hipEventRecord(e->tev[2 * e->t_used], e->stream) : hipSuccess; }
+    hipError_t end() {
+        if (!on) return hipSuccess;
+        const hipError_t st = hipEventRecord(e->tev[2 * e->t_used + 1], e->stream);
+        ++e->t_used;
+        return st;
+    }
+};
+
+// The bumps of validated events: unjoined observers dropped, equal keys merged,
+// one launch.  Every step is a saturating add of a positive amount, so the
+// merged add equals the steps one at a time.
+int tag_apply(gsx_engine* e, const gsx_tag_event* ev, size_t n) {
+    auto& G = e->tagt;
+    std::map<std::pair<uint64_t, uint32_t>, uint64_t> sum;
+    for (size_t i = 0; i < n; ++i)
+        if (ev[i].count && tag_joined(e, e->pair_obs[ev[i].pair], ev[i].topic))  // bumpDeliveryTag fails, :146-149
+            sum[{ev[i].pair, ev[i].topic}] += ev[i].count;
+    if (sum.empty()) return GSX_OK;
+    std::vector<gsx::DevTagEvent> dev;
+    dev.reserve(sum.size());
+    for (const auto& kv : sum) {
+        const uint64_t add = std::min<uint64_t>(kv.second, G.p.cap) * G.p.bump;  // (count beyond cap changes nothing)
+        dev.push_back({kv.first.first, kv.first.second, (uint32_t)std::min<uint64_t>(add, G.p.cap)});
+    }
+    const size_t bytes = sizeof(gsx::DevTagEvent) * dev.size();
+    if (G.ev_bytes < bytes) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (G.ev) (void)hipFree(G.ev);
+        G.ev = nullptr;
+        G.ev_bytes = 0;
+        const size_t want = std::max<size_t>(2 * bytes, 4096);
+        HIPCHK(e, hipMalloc(&G.ev, want));
+        G.ev_bytes = want;
+    }
+    HIPCHK(e, hipMemcpyAsync(G.ev, dev.data(), bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, gsx::launch_tag_events(dev_tags(e), static_cast<const gsx::DevTagEvent*>(G.ev), (uint32_t)dev.size(),
+                                     e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));  // (the host vector was the copy's source)
+    return GSX_OK;
+}
+
+int tag_trace_check(gsx_engine* e, uint64_t pair, uint32_t topic) {
+    if (int rc = gx_busy(e)) return rc;
+    if (int rc = tag_on(e)) return rc;
+    if (int rc = check_pair(e, pair)) return rc;
+    if (topic >= e->T) return fail(e, GSX_EINVAL, "topic out of range");
+    return GSX_OK;
+}
+}  // namespace
+
+// tag_tracer.go:13-31
+int gsx_default_tag_params(gsx_tag_params* p) {
+    if (!p) return GSX_EINVAL;
+    *p = gsx_tag_params{};
+    p->bump = 1;
+    p->decay_amount = 1;
+    p->cap = 15;
+    p->decay_interval_ns = 10 * 60 * kSecond;
+    return GSX_OK;
+}
+
+int gsx_set_tag_params(gsx_engine* e, const gsx_tag_params* p) {
+    if (!e) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    if (p && !(p->bump >= 1 && p->bump <= p->cap && p->cap <= 255 && p->decay_amount >= 1))
+        return fail(e, GSX_EINVAL, "tag params: 1 <= bump <= cap <= 255 and decay_amount >= 1");
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    tag_free(e);
+    if (!p) return GSX_OK;
+    auto& G = e->tagt;
+    G.p = *p;
+    const size_t bytes = std::max<size_t>((size_t)e->n_tiles * e->T * gsx::TILE, 64);
+    std::vector<uint32_t> lr;
+    for (uint32_t u = 0; u < e->n_nodes; ++u)
+        if (e->row_ptr[u + 1] - e->row_ptr[u] > (int64_t)gsx::CONN_LONG_ROW) lr.push_back(u);
+    int rc = 0;
+    if ((rc = dalloc(e, &G.tags, bytes)) || (rc = dalloc(e, &G.long_rows, lr.size()))) {
+        tag_free(e);
+        return rc;
+    }
+    hipError_t st = hipMemsetAsync(G.tags, 0, bytes, e->stream);
+    if (st == hipSuccess && !lr.empty())
+        st = hipMemcpyAsync(G.long_rows, lr.data(), 4 * lr.size(), hipMemcpyHostToDevice, e->stream);
+    const hipError_t st2 = hipStreamSynchronize(e->stream);
+    if (st != hipSuccess || st2 != hipSuccess) {
+        tag_free(e);
+        HIPCHK(e, st);
+        HIPCHK(e, st2);
+    }
+    G.n_long = (uint32_t)lr.size();
+    G.on = true;
+    return GSX_OK;
+}
+
+// ValidateMessage, tag_tracer.go:213-223
+int gsx_tag_trace_validate(gsx_engine* e, uint64_t pair, uint64_t msg_id, uint32_t topic, int64_t now) {
+    (void)now;
+    if (!e) return GSX_EINVAL;
+    if (int rc = tag_trace_check(e, pair, topic)) return rc;
+    (void)e->tagt.near[{e->pair_obs[pair], msg_id}];
+    return GSX_OK;
+}
+
+// DuplicateMessage, tag_tracer.go:225-235
+int gsx_tag_trace_duplicate(gsx_engine* e, uint64_t pair, uint64_t msg_id, uint32_t topic, int64_t now) {
+    (void)now;
+    if (!e) return GSX_EINVAL;
+    if (int rc = tag_trace_check(e, pair, topic)) return rc;
+    auto it = e->tagt.near.find({e->pair_obs[pair], msg_id});
+    if (it == e->tagt.near.end()) return GSX_OK;
+    if (std::find(it->second.begin(), it->second.end(), pair) == it->second.end()) it->second.push_back(pair);
+    return GSX_OK;
+}
+
+// DeliverMessage, tag_tracer.go:187-199
+int gsx_tag_trace_deliver(gsx_engine* e, uint64_t pair, uint64_t msg_id, uint32_t topic, int64_t now) {
+    (void)now;
+    if (!e) return GSX_EINVAL;
+    if (int rc = tag_trace_check(e, pair, topic)) return rc;
+    std::vector<gsx_tag_event> ev{{pair, topic, 1}};
+    auto it = e->tagt.near.find({e->pair_obs[pair], msg_id});
+    if (it != e->tagt.near.end()) {
+        for (uint64_t q : it->second) ev.push_back({q, topic, 1});
+        e->tagt.near.erase(it);
+    }
+    return tag_apply(e, ev.data(), ev.size());
+}
+
+// RejectMessage, tag_tracer.go:237-252
+int gsx_tag_trace_reject(gsx_engine* e, uint64_t pair, uint64_t msg_id, uint32_t topic, int32_t reason, int64_t now) {
+    (void)now;
+    if (!e) return GSX_EINVAL;
+    if (int rc = tag_trace_check(e, pair, topic)) return rc;
+    if (reason < GSX_REJECT_BLACKLISTED_PEER || reason > GSX_REJECT_SELF_ORIGIN)
+        return fail(e, GSX_EINVAL, "unknown reject reason");
+    if (reason == GSX_REJECT_VALIDATION_THROTTLED || reason == GSX_REJECT_VALIDATION_IGNORED ||
+        reason == GSX_REJECT_VALIDATION_FAILED)
+        e->tagt.near.erase({e->pair_obs[pair], msg_id});
+    return GSX_OK;
+}
+
+int gsx_tag_num_pending(gsx_engine* e, uint64_t* out) {
+    if (!e || !out) return GSX_EINVAL;
+    if (int rc = tag_on(e)) return rc;
+    *out = e->tagt.near.size();
+    return GSX_OK;
+}
+
+int gsx_tag_events(gsx_engine* e, const gsx_tag_event* ev, size_t n) {
+    if (!e || (n && !ev)) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    if (int rc = tag_on(e)) return rc;
+    for (size_t i = 0; i < n; ++i)
+        if (ev[i].pair >= e->E || ev[i].topic >= e->T) return fail(e, GSX_EINVAL, "tag event pair or topic out of range");
+    return tag_apply(e, ev, n);
+}
+
+int gsx_tag_decay(gsx_engine* e, uint64_t steps) {
+    if (!e) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    if (int rc = tag_on(e)) return rc;
+    const uint64_t sub = std::min<uint64_t>(steps, 255) * e->tagt.p.decay_amount;  // (a tag is at most 255)
+    TagRegion reg(e);
+    HIPCHK(e, reg.begin());
+    HIPCHK(e, gsx::launch_tag_decay(dev_tags(e), (uint32_t)std::min<uint64_t>(sub, 255), e->stream));
+    HIPCHK(e, reg.end());
+    return GSX_OK;
+}
+
+int gsx_tag_fold_prop(gsx_engine* e) {
+    if (!e) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    auto& G = e->tagt;
+    auto& P = e->prop;
+    if (int rc = tag_on(e)) return rc;
+    if (!P.have_last) return fail(e, GSX_ESTATE, "no propagation call yet");
+    if (P.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
+    if (e->sharded()) return fail(e, GSX_ESTATE, "the tag tracer folds propagations of unsharded engines only");
+    gsx::PropState ps = P.last;
+    if (!ps.from_mask)
+        return fail(e, GSX_ESTATE, "first deliverers were not tracked in the last call (gsx_prop_set_tracking)");
+    ps.n_rows = P.rows_valid;
+    const uint32_t W = ps.n_words, m = ps.n_msgs;
+    if (m == 0 || e->E == 0) return GSX_OK;
+    if (P.vals.size() != m) return fail(e, GSX_ESTATE, "the last call's validation outcomes are gone");
+    if (P.cfg.topic >= e->T) return fail(e, GSX_ESTATE, "the last call's topic is not one of the engine's");
+    ps.topic = P.cfg.topic;
+    const bool near = P.cfg.validation_delay_ns > 0;
+    std::vector<uint64_t> acc(W, 0);
+    for (uint32_t k = 0; k < m; ++k)
+        if (P.vals[k] == GSX_VALIDATION_ACCEPT || P.vals[k] > GSX_VALIDATION_THROTTLE) acc[k / 64] |= 1ull << (k % 64);
+    const size_t need = (near ? (size_t)e->E * W : 0) + W;
+    if (G.fold_cap < need) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (G.fold_buf) (void)hipFree(G.fold_buf);
+        G.fold_buf = nullptr;
+        G.fold_cap = 0;
+        if (int rc = dalloc(e, &G.fold_buf, need)) return rc;
+        G.fold_cap = need;
+    }
+    uint64_t* const d_acc = G.fold_buf;
+    uint64_t* const d_dup = G.fold_buf + W;
+    TagRegion reg(e);
+    hipError_t st = hipMemcpyAsync(d_acc, acc.data(), 8 * acc.size(), hipMemcpyHostToDevice, e->stream);
+    if (st == hipSuccess) st = reg.begin();
+    if (st == hipSuccess && near) st = gsx::launch_prop_dup_rows(ps, d_dup, e->stream);
+    if (st == hipSuccess) st = gsx::launch_tag_fold(dev_tags(e), ps, near ? d_dup : nullptr, d_acc, near ? 1 : 0, e->stream);
+    if (st == hipSuccess) st = reg.end();
+    const hipError_t st2 = hipStreamSynchronize(e->stream);  // (acc was the copy's source)
+    HIPCHK(e, st);
+    HIPCHK(e, st2);
+    return GSX_OK;
+}
+
+int gsx_tag_export(gsx_engine* e, uint8_t* tags) {
+    if (!e || !tags) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    auto& G = e->tagt;
+    if (int rc = tag_on(e)) return rc;
+    const size_t n = (size_t)e->E * e->T;
+    if (n == 0) return GSX_OK;
+    if (!G.exp_buf)
+        if (int rc = dalloc(e, &G.exp_buf, n)) return rc;
+    HIPCHK(e, gsx::launch_tag_export(dev_tags(e), G.exp_buf, e->stream));
+    HIPCHK(e, hipMemcpyAsync(tags, G.exp_buf, n, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GSX_OK;
+}
+
+int gsx_conn_values(gsx_engine* e, uint32_t* value, uint8_t* protect) {
+    static_assert(gsx::CONN_DIRECT == GSX_CONN_DIRECT && gsx::CONN_MESH == GSX_CONN_MESH,
+                  "the kernel's constants are the header's");
+    if (!e) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    auto& G = e->tagt;
+    if (int rc = tag_on(e)) return rc;
+    if ((!value && !protect) || e->E == 0) return GSX_OK;
+    if (int rc = flush(e)) return rc;  // queued Graft / Prune / AddPeer events move the protection bits
+    const bool h_val = value && !on_device(value), h_prot = protect && !on_device(protect);
+    if (h_val && !G.val_buf)
+        if (int rc = dalloc(e, &G.val_buf, e->E)) return rc;
+    if (h_prot && !G.prot_buf)
+        if (int rc = dalloc(e, &G.prot_buf, e->E)) return rc;
+    uint32_t* const d_val = h_val ? G.val_buf : value;
+    uint8_t* const d_prot = h_prot ? G.prot_buf : protect;
+    TagRegion reg(e);
+    HIPCHK(e, reg.begin());
+    HIPCHK(e, gsx::launch_conn_values(dev_tags(e), d_val, d_prot, nullptr, e->stream));
+    HIPCHK(e, reg.end());
+    if (h_val) HIPCHK(e, hipMemcpyAsync(value, d_val, 4 * e->E, hipMemcpyDeviceToHost, e->stream));
+    if (h_prot) HIPCHK(e, hipMemcpyAsync(protect, d_prot, e->E, hipMemcpyDeviceToHost, e->stream));
+    if (h_val || h_prot) HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GSX_OK;
+}
+
+int gsx_conn_trim(gsx_engine* e, uint32_t low_water, uint8_t* trim, uint32_t* node_trimmed) {
+    if (!e || !trim) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    auto& G = e->tagt;
+    if (int rc = tag_on(e)) return rc;
+    if (e->sharded()) return fail(e, GSX_ESTATE, "connections are trimmed on unsharded engines only");
+    if (e->n_nodes == 0) return GSX_OK;
+    if (int rc = flush(e)) return rc;
+    const bool h_trim = !on_device(trim), h_nt = !node_trimmed || !on_device(node_trimmed);
+    if (!G.key)
+        if (int rc = dalloc(e, &G.key, e->E)) return rc;
+    if (h_trim && !G.trim_buf)
+        if (int rc = dalloc(e, &G.trim_buf, e->E)) return rc;
+    if (h_nt && !G.nt_buf)
+        if (int rc = dalloc(e, &G.nt_buf, e->n_nodes)) return rc;
+    uint8_t* const d_trim = h_trim ? G.trim_buf : trim;
+    uint32_t* const d_nt = h_nt ? G.nt_buf : node_trimmed;
+    const gsx::TagState t = dev_tags(e);
+    TagRegion reg(e);
+    HIPCHK(e, reg.begin());
+    HIPCHK(e, gsx::launch_conn_values(t, nullptr, nullptr, G.key, e->stream));
+    HIPCHK(e, gsx::launch_conn_trim(t, e->d_row_ptr, G.key, low_water, G.long_rows, G.n_long, d_trim, d_nt, e->stream));
+    HIPCHK(e, reg.end());
+    if (h_trim && e->E) HIPCHK(e, hipMemcpyAsync(trim, d_trim, e->E, hipMemcpyDeviceToHost, e->stream));
+    if (node_trimmed && h_nt)
+        HIPCHK(e, hipMemcpyAsync(node_trimmed, d_nt, 4 * (size_t)e->n_nodes, hipMemcpyDeviceToHost, e->stream));
+    if (h_trim || (node_trimmed && h_nt)) HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GSX_OK;
+}
+
 int gsx_prop_duplicates(gsx_engine* e, uint64_t* rows, size_t n_words) {
     if (!e || !rows) return GSX_EINVAL;
     if (!e->prop.have_last) return fail(e, GSX_ESTATE, "no gsx_propagate call yet");
@@ -6402,6 +6756,7 @@ int gsx_set_subscriptions(gsx_engine* e, const uint64_t* joined) {
     for (uint32_t v = 0; v < e->n_nodes; ++v) e->h_sub[v] = joined[v] & all;
     HIPCHK(e, hipMemcpy(e->d_sub, e->h_sub.data(), 8 * (size_t)e->n_nodes, hipMemcpyHostToDevice));
     HIPCHK(e, gsx::launch_psub(e->d_col, e->d_sub, e->d_psub, e->E, e->stream));
+    if (e->tagt.on) HIPCHK(e, gsx::launch_tag_clear_unjoined(dev_tags(e), e->stream));  // tag_tracer.go:128-140
     HIPCHK(e, hipStreamSynchronize(e->stream));
     ++e->mem_gen;
     return GSX_OK;
@@ -6460,6 +6815,7 @@ int member_round(gsx_engine* e, const uint32_t* nodes, const uint32_t* topics, s
     }
     HIPCHK(e, hipMemcpy(e->d_sub, e->h_sub.data(), 8 * (size_t)e->n_nodes, hipMemcpyHostToDevice));
     HIPCHK(e, gsx::launch_psub(e->d_col, e->d_sub, e->d_psub, e->E, e->stream));
+    if (leave && e->tagt.on) HIPCHK(e, gsx::launch_tag_clear_unjoined(dev_tags(e), e->stream));  // tag_tracer.go:128-140
     ++e->mem_gen;
     // a heartbeat's buffers and state, without maintenance or gossip
     if (int rc = hb_begin_state(e, 0, now, seed, true)) return rc;

@@ -469,6 +469,41 @@ class GaterView(C.Structure):
     ]
 
 
+# the tag tracer (tag_tracer.go) and connection trims
+GSX_CONN_DIRECT = 1
+GSX_CONN_MESH = 2
+
+
+class TagParams(C.Structure):
+    """gsx_tag_params: the GossipSubConnTag* settings, tag_tracer.go:13-31"""
+
+    _fields_ = [
+        ("bump", C.c_uint32),
+        ("decay_amount", C.c_uint32),
+        ("cap", C.c_uint32),
+        ("decay_interval_ns", C.c_int64),
+    ]
+
+
+class TagEvent(C.Structure):
+    """gsx_tag_event"""
+
+    _fields_ = [("pair", C.c_uint64), ("topic", C.c_uint32), ("count", C.c_uint32)]
+
+
+TAG_EVENT_DTYPE = None
+
+
+def tag_event_dtype():
+    global TAG_EVENT_DTYPE
+    if TAG_EVENT_DTYPE is None:
+        import numpy as np
+
+        TAG_EVENT_DTYPE = np.dtype([("pair", "<u8"), ("topic", "<u4"), ("count", "<u4")], align=True)
+        assert TAG_EVENT_DTYPE.itemsize == C.sizeof(TagEvent)
+    return TAG_EVENT_DTYPE
+
+
 P = C.POINTER
 _u64p = P(C.c_uint64)
 
@@ -628,6 +663,20 @@ SIGNATURES = {
     "gsx_gater_fold_prop": (C.c_int, [C.c_void_p]),
     "gsx_gater_enforce": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_gater_gate_pairs": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]),
+    "gsx_default_tag_params": (C.c_int, [P(TagParams)]),
+    "gsx_set_tag_params": (C.c_int, [C.c_void_p, P(TagParams)]),
+    "gsx_tag_trace_validate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int64]),
+    "gsx_tag_trace_duplicate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int64]),
+    "gsx_tag_trace_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int64]),
+    "gsx_tag_trace_reject": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, C.c_int64]),
+    "gsx_tag_num_pending": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
+    "gsx_tag_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "gsx_tag_decay": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "gsx_tag_fold_prop": (C.c_int, [C.c_void_p]),
+    "gsx_tag_export": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # (outputs: host or device addresses, None skips one)
+    "gsx_conn_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsx_conn_trim": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "gsx_timing_begin": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_timing_end": (
         C.c_int,

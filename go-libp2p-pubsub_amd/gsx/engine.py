@@ -189,6 +189,24 @@ class ScoreStats:
                           both(self.peer_min, other.peer_min, np.minimum))
 
 
+class ConnTrim:
+    """A forced trim of every observer's connections (gsx_conn_trim): trim[p] = 1
+    for the pairs it closes, node_trimmed[u] their number in u's row;
+    trimmed(u) / kept(u) -> the pair indices of u's present and connected pairs
+    the trim closes / keeps."""
+
+    def __init__(self, row_ptr, trim, node_trimmed, conns):
+        self.row_ptr, self.trim, self.node_trimmed, self.conns = row_ptr, trim, node_trimmed, conns
+
+    def trimmed(self, u: int):
+        b, e = int(self.row_ptr[u]), int(self.row_ptr[u + 1])
+        return b + np.nonzero(self.trim[b:e])[0]
+
+    def kept(self, u: int):
+        b, e = int(self.row_ptr[u]), int(self.row_ptr[u + 1])
+        return b + np.nonzero(self.conns[b:e] & (self.trim[b:e] == 0))[0]
+
+
 class Engine:
     def __init__(self, n_topics: int, device: int = 0):
         self.lib = abi.load_library()
@@ -253,6 +271,7 @@ class Engine:
         self.n_nodes = n
         self.node_lo = 0
         self.n_total = n
+        self._row_ptr = row_ptr.copy()  # (ConnTrim's rows)
 
     def set_ip_whitelist(self, ips: Iterable[int]):
         a = np.ascontiguousarray(list(ips), dtype=np.uint32)
@@ -438,6 +457,83 @@ class Engine:
         self._chk(self.lib.gsx_gater_gate_pairs(self.h, C.byref(a), C.byref(b)), "gsx_gater_gate_pairs")
         return int(a.value), int(b.value)
 
+    # -- the tag tracer and connection trims (gsx.h; tag_tracer.go) ------------------------
+    def default_tag_params(self) -> "abi.TagParams":
+        p = abi.TagParams()
+        self._chk(self.lib.gsx_default_tag_params(C.byref(p)), "gsx_default_tag_params")
+        return p
+
+    def set_tag_params(self, p: "abi.TagParams | None"):
+        """gsx_set_tag_params: a fresh tag tracer for the loaded overlay; None drops it."""
+        self._chk(self.lib.gsx_set_tag_params(self.h, C.byref(p) if p is not None else None), "gsx_set_tag_params")
+
+    def tag_trace_validate(self, pair, msg, topic, now):
+        self._chk(self.lib.gsx_tag_trace_validate(self.h, pair, msg, topic, now), "gsx_tag_trace_validate")
+
+    def tag_trace_duplicate(self, pair, msg, topic, now):
+        self._chk(self.lib.gsx_tag_trace_duplicate(self.h, pair, msg, topic, now), "gsx_tag_trace_duplicate")
+
+    def tag_trace_deliver(self, pair, msg, topic, now):
+        self._chk(self.lib.gsx_tag_trace_deliver(self.h, pair, msg, topic, now), "gsx_tag_trace_deliver")
+
+    def tag_trace_reject(self, pair, msg, topic, reason, now):
+        if isinstance(reason, str):
+            reason = abi.REJECT_REASONS[reason]
+        self._chk(self.lib.gsx_tag_trace_reject(self.h, pair, msg, topic, reason, now), "gsx_tag_trace_reject")
+
+    def tag_num_pending(self) -> int:
+        v = C.c_uint64()
+        self._chk(self.lib.gsx_tag_num_pending(self.h, C.byref(v)), "gsx_tag_num_pending")
+        return int(v.value)
+
+    def tag_events(self, events):
+        """gsx_tag_events: rows of abi.tag_event_dtype() (pair, topic, count), or (pair, topic, count) tuples."""
+        ev = np.ascontiguousarray(events, dtype=abi.tag_event_dtype())
+        self._chk(self.lib.gsx_tag_events(self.h, ev.ctypes.data_as(C.c_void_p), len(ev)), "gsx_tag_events")
+
+    def tag_decay(self, steps: int = 1):
+        self._chk(self.lib.gsx_tag_decay(self.h, steps), "gsx_tag_decay")
+
+    def tag_fold_prop(self):
+        """gsx_tag_fold_prop: the last propagation's deliveries as the tag tracer's calls."""
+        self._chk(self.lib.gsx_tag_fold_prop(self.h), "gsx_tag_fold_prop")
+
+    def tag_export(self):
+        """gsx_tag_export -> [n_topics, n_pairs] u8"""
+        out = np.zeros(max(self.n_topics * self.n_pairs, 1), dtype=np.uint8)
+        self._chk(self.lib.gsx_tag_export(self.h, out.ctypes.data_as(C.c_void_p)), "gsx_tag_export")
+        return out[: self.n_topics * self.n_pairs].reshape(self.n_topics, self.n_pairs)
+
+    def conn_values(self, value_ptr=None, protect_ptr=None):
+        """gsx_conn_values -> (value [n_pairs] u32, protect [n_pairs] u8 of GSX_CONN_* bits).
+        With a device pointer or tensor for either, both go there in stream order; then -> None."""
+        if value_ptr is not None or protect_ptr is not None:
+            self._chk(self.lib.gsx_conn_values(self.h, self._p(value_ptr), self._p(protect_ptr)), "gsx_conn_values")
+            return None
+        v = np.zeros(max(self.n_pairs, 1), dtype=np.uint32)
+        p = np.zeros(max(self.n_pairs, 1), dtype=np.uint8)
+        self._chk(self.lib.gsx_conn_values(self.h, v.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p)),
+                  "gsx_conn_values")
+        return v[: self.n_pairs], p[: self.n_pairs]
+
+    def conn_trim(self, low_water: int, trim_ptr=None, node_trimmed_ptr=None):
+        """gsx_conn_trim -> ConnTrim.  With a device pointer or tensor for the trim bytes (and
+        optionally the per-node counts) they are written in stream order; then -> None."""
+        if trim_ptr is not None:
+            self._chk(self.lib.gsx_conn_trim(self.h, low_water, self._p(trim_ptr), self._p(node_trimmed_ptr)),
+                      "gsx_conn_trim")
+            return None
+        t = np.zeros(max(self.n_pairs, 1), dtype=np.uint8)
+        nt = np.zeros(max(self.n_nodes, 1), dtype=np.uint32)
+        self._chk(self.lib.gsx_conn_trim(self.h, low_water, t.ctypes.data_as(C.c_void_p),
+                                         nt.ctypes.data_as(C.c_void_p)), "gsx_conn_trim")
+        pf = np.zeros(max(self.n_pairs, 1), dtype=np.uint8)
+        sv = abi.StateView()
+        sv.pair_flags = pf.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._chk(self.lib.gsx_export_state(self.h, C.byref(sv)), "gsx_export_state")
+        both = abi.GSX_PAIR_PRESENT | abi.GSX_PAIR_CONNECTED
+        return ConnTrim(self._row_ptr, t[: self.n_pairs], nt[: self.n_nodes], (pf[: self.n_pairs] & both) == both)
+
     # -- stepped / sharded propagation (gsx.h "range sharding") --------------------------
     def load_overlay_shard(self, n_total, node_lo, row_ptr, col, edge_flags=None, node_ips=None):
         row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
@@ -454,6 +550,7 @@ class Engine:
         self._chk(self.lib.gsx_num_pairs(self.h, C.byref(v)), "gsx_num_pairs")
         self.n_pairs = int(v.value)
         self.n_nodes = n
+        self._row_ptr = row_ptr.copy()
         self.node_lo = node_lo
         self.n_total = n_total
 

@@ -1389,6 +1389,113 @@ int gsx_gater_enforce(gsx_engine* e, uint32_t on);
  * pointer may be NULL).  GSX_ESTATE: no decision set. */
 int gsx_gater_gate_pairs(gsx_engine* e, uint64_t* none, uint64_t* control);
 
+/* ---- the tag tracer and connection trims (tag_tracer.go) ---------------------- */
+/* The third RawTracer of the router: what the connection manager listens to
+ * when it decides which connections survive a trim.  Per (pair, topic) one
+ * decaying delivery tag (a u8: BumpSumBounded(0, cap) / DecayFixed(amount),
+ * tag_tracer.go:107-126), bumped for the first deliverer of a message and for
+ * the near-first ones whose duplicate arrived while the first copy was still
+ * validating (:187-199).  Protection is not stored twice: pubsub:<direct>
+ * (:81-91, 179-181) is GSX_EDGE_DIRECT of a present pair, pubsub:<topic>
+ * (:93-101, 205-211) is the scorer's in-mesh bit of (pair, topic), which the
+ * same Graft / Prune traces keep.
+ *
+ * Invariant: the tag of (u -> v, t) is 0 whenever u has not joined t (Leave
+ * closes the topic's tag, :128-140; a bump at an unjoined observer fails,
+ * :146-149).  While the tracer is on, gsx_leave clears the leavers' tags of
+ * the topic and gsx_set_subscriptions those of every unit it un-joins; a bump
+ * at an unjoined observer is dropped by every call below.
+ *
+ * The tracer is off by default; nothing else in the engine reads it.  Out of
+ * scope: the fold and the trim on range shards and message-parallel replicas;
+ * dialling or closing connections (the overlay stays fixed: gsx_conn_trim
+ * says which pairs a trim would close); a C++ pubsub::TagTracer mirror. */
+typedef struct gsx_tag_params {
+    uint32_t bump;             /* GossipSubConnTagBumpMessageDelivery, :20 */
+    uint32_t decay_amount;     /* GossipSubConnTagDecayAmount, :26         */
+    uint32_t cap;              /* GossipSubConnTagMessageDeliveryCap, :30  */
+    int64_t decay_interval_ns; /* GossipSubConnTagDecayInterval, :23: carried for the caller, who
+                                  calls gsx_tag_decay; the engine never reads a clock */
+} gsx_tag_params;
+/* 1 / 1 / 15 / 10 min (:13-31). */
+int gsx_default_tag_params(gsx_tag_params* out);
+/* newTagTracer (:58-70) for the loaded overlay: every tag 0, no pending
+ * message.  NULL drops the tracer, as loading an overlay and gsx_destroy do.
+ * GSX_EINVAL unless 1 <= bump <= cap <= 255 and decay_amount >= 1.
+ * GSX_ESTATE: no overlay loaded. */
+int gsx_set_tag_params(gsx_engine* e, const gsx_tag_params* p);
+
+/* The tracer's message traces, with the arguments of the scorer's gsx_trace_*.
+ * The nearFirst map (:53-55) lives on the host, keyed by (observer, msg_id):
+ *   validate   ValidateMessage :213-223: creates the entry if absent;
+ *   duplicate  DuplicateMessage :225-235: adds the pair to an existing entry (a set);
+ *   deliver    DeliverMessage :187-199: bumps the pair and every recorded
+ *              near-first pair on `topic`, then deletes the entry;
+ *   reject     RejectMessage :237-252: deletes the entry for the validation
+ *              throttled / ignored / failed reasons, nothing for the others.
+ * GSX_ESTATE: no tracer.  GSX_ERANGE: pair out of range.  GSX_EINVAL: topic
+ * >= n_topics, an unknown reject reason. */
+int gsx_tag_trace_validate(gsx_engine* e, uint64_t pair, uint64_t msg_id, uint32_t topic, int64_t now_ns);
+int gsx_tag_trace_duplicate(gsx_engine* e, uint64_t pair, uint64_t msg_id, uint32_t topic, int64_t now_ns);
+int gsx_tag_trace_deliver(gsx_engine* e, uint64_t pair, uint64_t msg_id, uint32_t topic, int64_t now_ns);
+int gsx_tag_trace_reject(gsx_engine* e, uint64_t pair, uint64_t msg_id, uint32_t topic, int32_t reason,
+                         int64_t now_ns);
+/* Live nearFirst entries (messages validating somewhere). */
+int gsx_tag_num_pending(gsx_engine* e, uint64_t* out);
+
+/* `count` bumps of tag (pair, topic): tag = min(cap, tag + count * bump)
+ * (bumpDeliveryTag, :142-151). */
+typedef struct gsx_tag_event {
+    uint64_t pair;
+    uint32_t topic;
+    uint32_t count;
+} gsx_tag_event;
+/* Applies the events on the device.  The host merges equal (pair, topic) keys
+ * first (every step is a saturating add of a positive amount, so the merged
+ * add equals the steps one at a time in the given order), then one lane owns
+ * each key: no atomics, bit-identical from run to run.  GSX_EINVAL: a pair or
+ * topic out of range (nothing is applied).  GSX_ESTATE: no tracer. */
+int gsx_tag_events(gsx_engine* e, const gsx_tag_event* ev, size_t n);
+/* DecayFixed (:118) for `steps` intervals: every tag becomes max(0, tag -
+ * steps * decay_amount), one streaming pass over the tag bytes. */
+int gsx_tag_decay(gsx_engine* e, uint64_t steps);
+/* Folds the last propagation of an unsharded engine into the tags, as the
+ * tracer calls of that batch would have, defined on the call's public
+ * results.  For pair p = (u -> v), the call's topic t and each ACCEPT message
+ * k, one bump of tag (p, t)
+ *   when first_from(k, u) == v (gsx_prop_results), and
+ *   when p's bit of k in gsx_prop_duplicates is set, the call's
+ *   validation_delay_ns > 0 and hop(k, v) + 1 == hop(k, u): that copy came in
+ *   the hop of the first copy, so while u was validating (with a zero delay
+ *   validation is inline and nothing is near-first).
+ * Messages that were not accepted bump nothing; bumps at an observer that has
+ * not joined t are dropped; a source's own hop 0 bumps nothing.  One lane per
+ * pair writes its own byte: no atomics, no host round trip.  A second call
+ * folds the same batch again.  GSX_ESTATE: no tracer, no propagation yet, a
+ * stepped call in flight, a range shard, or first-deliverer tracking off in
+ * that call. */
+int gsx_tag_fold_prop(gsx_engine* e);
+/* The tags, topic-major [t * n_pairs + p] like gsx_export_state, to host memory. */
+int gsx_tag_export(gsx_engine* e, uint8_t* tags);
+
+#define GSX_CONN_DIRECT 1u /* protect bit 0: pubsub:<direct> */
+#define GSX_CONN_MESH 2u   /* protect bit 1: some pubsub:<topic> */
+/* Per pair: value = the sum over topics of its tags (GetTagInfo(p).Value as
+ * far as this tracer feeds it), protect = GSX_CONN_* bits.  A pair the scorer
+ * holds no peerStats for gives 0 / 0.  Either pointer may be NULL; each may be
+ * host or device memory, as gsx_score_stats takes its outputs.  The scorer's
+ * queued events are applied first.  GSX_ESTATE: no tracer. */
+int gsx_conn_values(gsx_engine* e, uint32_t* value, uint8_t* protect);
+/* A forced TrimOpenConns per observer row.  C = the row's present and
+ * connected pairs.  If |C| > low_water, trim[p] = 1 for the first min(|C| -
+ * low_water, unprotected pairs of C) unprotected pairs of C in ascending
+ * (value, pair index) order; every other byte is 0.  node_trimmed[u] = the
+ * number marked in u's row (may be NULL).  The connection manager is not part
+ * of the reference tree: this contract (no grace or silence period, ties by
+ * index) is the engine's own.  Outputs may be host or device memory.
+ * GSX_ESTATE: no tracer, a range shard. */
+int gsx_conn_trim(gsx_engine* e, uint32_t low_water, uint8_t* trim, uint32_t* node_trimmed);
+
 #ifdef __cplusplus
 }
 #endif
