@@ -414,6 +414,49 @@ hipError_t launch_prop_hops_export(const PropState& ps, uint8_t* hop_mn, hipStre
 constexpr uint32_t PROP_STATS_HOPS = 65;  // GSX_MAX_HOPS + 1
 hipError_t launch_prop_stats(const PropState& ps, uint32_t* msg_hop_hist, uint32_t* node_received,
                              unsigned long long* node_hop_sum, hipStream_t st);
+// gsx_propagate_timed (gsx_prop_timed.hip): propagation on a tick clock with a
+// latency per directed link.  The call's setup (fwd / pin / compacted senders)
+// is the PropState's, built by launch_prop_fwd; everything else is here.
+// A send row of tick f lives in ring slot f mod R (valid under its rocc bit),
+// a "some sender's copy reaches you at tick a" bit in mark slot a mod R; R is
+// a power of two >= largest latency + vd + 2, so the kernel of tick t can
+// clear the slots the next tick reuses (mark slot t - 1, rocc slot t + 1 + vd)
+// while nobody reads or writes them.
+enum {
+    TS_DELIV = 0,   // accepted first receipts
+    TS_DUPS,        // receipts of an already seen message
+    TS_DUPS_IN,     // ... inside the P3 window
+    TS_REJ,
+    TS_IGN,
+    TS_GRAY,        // copies the receiver's AcceptFrom drops
+    TS_LAST_TICK,   // last tick with a first receipt (max)
+    TS_LAST_COPY,   // last arrival tick of any copy sent (max; <= max_ticks)
+    TS_MARKED,      // marked nodes the tick kernels walked
+    TS_WORDS
+};
+struct TimedState {
+    uint64_t* ring;      // [R][node][W] send rows
+    uint64_t* rocc;      // [R][node / 64] ring occupancy
+    uint64_t* mark;      // [R][node / 64] receivers of a tick
+    uint64_t* seen;      // [node][W]
+    uint64_t* origin;    // [node][W] messages the node published (zero elsewhere)
+    uint64_t* from;      // [pair (u -> v)][W] messages u first received from v
+    uint16_t* arr;       // [node][64 W] arrival ticks, 0xFFFF never
+    const uint8_t* lat;  // [pair (u -> v)] ticks of a copy v sends to u
+    uint32_t *fcnt, *dcnt, *icnt;  // per pair: first receipts, in-window duplicates, invalid deliveries
+    unsigned long long* stats;     // TS_*
+    uint32_t R, vd, max_ticks;
+    uint32_t lim;        // a duplicate at tick d of a first copy of tick a is inside the window iff d - a <= lim
+};
+hipError_t launch_timed_init(const PropState& ps, const TimedState& ts, hipStream_t st);
+hipError_t launch_timed_tick(const PropState& ps, const TimedState& ts, uint32_t t, hipStream_t st);
+// dst[q] += src[q] (the call's counts into the pending credit counts)
+hipError_t launch_timed_add(uint32_t* dst, const uint32_t* src, uint64_t n, hipStream_t st);
+hipError_t launch_timed_export(const PropState& ps, const TimedState& ts, uint16_t* tick_mn, hipStream_t st);
+// gsx_timed_stats: the outputs are added to (the caller zeroes them)
+hipError_t launch_timed_stats(const PropState& ps, const TimedState& ts, uint32_t bin_ticks, uint32_t n_bins,
+                              uint32_t* hist, uint32_t* node_received, unsigned long long* node_tick_sum,
+                              hipStream_t st);
 // gsx_score_stats (gsx_score_stats.hip): the selected pairs per score bin
 // (bin(s) = the edges k with !(s < edges[k]): a NaN in the top bin) for the
 // engine, per observer row and per peer, and the lowest selected score that

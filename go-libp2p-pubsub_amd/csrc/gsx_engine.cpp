@@ -430,6 +430,34 @@ struct gsx_engine {
     } prop;
     bool prop_track = true;  // gsx_prop_set_tracking: keep first-deliverer rows (gsx_prop_results)
 
+    // gsx_propagate_timed (gsx_prop_timed.hip): its own setup arrays (fwd / pin /
+    // compacted senders, rebuilt per call: gsx_propagate's incremental ones are
+    // not touched), the ring and the rows of gsx_device.h TimedState
+    struct {
+        uint8_t* lat = nullptr;  // gsx_set_link_latency, [pair]
+        uint32_t max_lat = 0;
+        uint8_t *fwd = nullptr, *rfwd = nullptr;
+        uint32_t *pin = nullptr, *cend = nullptr, *chg = nullptr, *nchg = nullptr;
+        uint2* cent = nullptr;
+        uint64_t* ndirty = nullptr;
+        unsigned long long *gray_pairs = nullptr, *stats = nullptr;
+        uint32_t *fcnt = nullptr, *dcnt = nullptr, *icnt = nullptr;
+        uint64_t *ring = nullptr, *rocc = nullptr, *mark = nullptr, *seen = nullptr, *origin = nullptr, *from = nullptr;
+        uint64_t* vmask = nullptr;
+        uint16_t* arr = nullptr;
+        gsx::DevMsg* msgs = nullptr;
+        size_t ring_words = 0, occ_words = 0, row_words = 0, from_words = 0, arr_cells = 0, msgs_cap = 0, vmask_words = 0;
+        gsx::PropState ps{};  // the last timed call
+        gsx::TimedState ts{};
+        bool have = false;   // a timed call's results are held
+        bool after = false;  // the last propagation was a timed call: gsx_propagate's result rows are not its
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint32_t* st_hist = nullptr;
+        size_t st_hist_cap = 0;
+        uint32_t* st_recv = nullptr;
+        unsigned long long* st_sum = nullptr;
+    } tprop;
+
     // the peer gater (gsx_set_gater_params; gsx_gater.hip): device arrays per
     // observer, per gater group (n_nodes "<unknown>" groups, then the engine's
     // (observer, IP) groups: grown with n_groups) and per pair
@@ -968,7 +996,21 @@ void tag_free(gsx_engine* e) {
     G = {};
 }
 
+void timed_free(gsx_engine* e) {
+    auto& T = e->tprop;
+    void* pp[] = {T.lat, T.fwd, T.rfwd, T.pin, T.cend, T.chg, T.nchg, T.cent, T.ndirty, T.gray_pairs, T.stats, T.fcnt,
+                  T.dcnt, T.icnt, T.ring, T.rocc, T.mark, T.seen, T.origin, T.from, T.vmask, T.arr, T.msgs, T.st_hist,
+                  T.st_recv, T.st_sum};
+    for (void* p : pp)
+        if (p) (void)hipFree(p);
+    hipEvent_t ev[2] = {T.ev[0], T.ev[1]};
+    T = {};
+    T.ev[0] = ev[0];
+    T.ev[1] = ev[1];
+}
+
 void free_state(gsx_engine* e) {
+    timed_free(e);
     if (e->vc_stream) (void)hipStreamSynchronize(e->vc_stream);  // (code-plane builds in flight)
     e->vc_busy[0] = e->vc_busy[1] = false;
     e->hist_idx = 0;
@@ -3048,6 +3090,30 @@ int fanout_publish(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_
     return GSX_OK;
 }
 
+// The per-pair arrays of propagation (allocated once per overlay; the pending
+// credit counts start empty).
+int prop_pair_buffers(gsx_engine* e) {
+    auto& P = e->prop;
+    if (P.fwd) return GSX_OK;
+    const size_t N = e->n_nodes, E = e->E;
+    int rc = 0;
+    P.chg_cap = (uint32_t)std::min<size_t>(std::max<size_t>(E / 16, 1024), 1u << 24);
+    if ((rc = dalloc(e, &P.fwd, E)) || (rc = dalloc(e, &P.pin, E)) || (rc = dalloc(e, &P.dup, E)) ||
+        (rc = dalloc(e, &P.corr, E)) || (rc = dalloc(e, &P.fcnt, E)) || (rc = dalloc(e, &P.flast, E)) ||
+        (rc = dalloc(e, &P.first, E)) || (rc = dalloc(e, &P.inv, E)) || (rc = dalloc(e, &P.gray_pairs, 1)) ||
+        (rc = dalloc(e, &P.cent, E)) || (rc = dalloc(e, &P.cend, std::max<size_t>(N, 1))) ||
+        (rc = dalloc(e, &P.rfwd, E)) ||
+        (rc = dalloc(e, &P.chg, P.chg_cap)) || (rc = dalloc(e, &P.nchg, 1)) ||
+        (rc = dalloc(e, &P.ndirty, (N + 63) / 64 + 1)))
+        return rc;
+    HIPCHK(e, hipMemsetAsync(P.nchg, 0, 4, e->stream));
+    HIPCHK(e, hipMemsetAsync(P.ndirty, 0, 8 * ((N + 63) / 64 + 1), e->stream));
+    HIPCHK(e, hipMemsetAsync(P.inv, 0, 4 * std::max<size_t>(E, 1), e->stream));
+    HIPCHK(e, hipMemsetAsync(P.dup, 0, 4 * std::max<size_t>(E, 1), e->stream));
+    HIPCHK(e, hipMemsetAsync(P.first, 0, 4 * std::max<size_t>(E, 1), e->stream));
+    return GSX_OK;
+}
+
 int prop_begin(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_config* cfg) {
     if (!e || !cfg || (m && !msgs)) return GSX_EINVAL;
     if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
@@ -3097,22 +3163,7 @@ int prop_begin(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_conf
             (rc = dalloc(e, &P.msgs, mm)) ||
             (rc = dalloc(e, &P.stats, (size_t)gsx::STAT_WORDS)))
             return rc;
-        if (!P.fwd) {
-            P.chg_cap = (uint32_t)std::min<size_t>(std::max<size_t>(E / 16, 1024), 1u << 24);
-            if ((rc = dalloc(e, &P.fwd, E)) || (rc = dalloc(e, &P.pin, E)) || (rc = dalloc(e, &P.dup, E)) ||
-                (rc = dalloc(e, &P.corr, E)) || (rc = dalloc(e, &P.fcnt, E)) || (rc = dalloc(e, &P.flast, E)) ||
-                (rc = dalloc(e, &P.first, E)) || (rc = dalloc(e, &P.inv, E)) || (rc = dalloc(e, &P.gray_pairs, 1)) ||
-                (rc = dalloc(e, &P.cent, E)) || (rc = dalloc(e, &P.cend, std::max<size_t>(N, 1))) ||
-                (rc = dalloc(e, &P.rfwd, E)) ||
-                (rc = dalloc(e, &P.chg, P.chg_cap)) || (rc = dalloc(e, &P.nchg, 1)) ||
-                (rc = dalloc(e, &P.ndirty, (N + 63) / 64 + 1)))
-                return rc;
-            HIPCHK(e, hipMemsetAsync(P.nchg, 0, 4, e->stream));
-            HIPCHK(e, hipMemsetAsync(P.ndirty, 0, 8 * ((N + 63) / 64 + 1), e->stream));
-            HIPCHK(e, hipMemsetAsync(P.inv, 0, 4 * std::max<size_t>(E, 1), e->stream));
-            HIPCHK(e, hipMemsetAsync(P.dup, 0, 4 * std::max<size_t>(E, 1), e->stream));
-            HIPCHK(e, hipMemsetAsync(P.first, 0, 4 * std::max<size_t>(E, 1), e->stream));
-        }
+        if ((rc = prop_pair_buffers(e))) return rc;
         P.words_cap = W;
         P.msgs_cap = (uint32_t)mm;
         P.rows_cap = rc_rows;
@@ -3280,6 +3331,7 @@ int prop_begin(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_conf
     }
     P.last = ps;
     P.have_last = true;
+    e->tprop.after = false;  // gsx_propagate's rows are this call's again
     P.cfg = *cfg;
     P.h = 0;
     P.global_last = UINT32_MAX;
@@ -4072,6 +4124,7 @@ int gsx_prop_set_tracking(gsx_engine* e, uint32_t first_deliverers) {
 int gsx_prop_results(gsx_engine* e, uint8_t* hop, int32_t* first_from) {
     if (!e) return GSX_EINVAL;
     if (!e->prop.have_last) return fail(e, GSX_ESTATE, "no gsx_propagate call yet");
+    if (e->tprop.after) return fail(e, GSX_ESTATE, "the last propagation was a timed call (gsx_timed_results / gsx_timed_stats)");
     gsx::PropState ps = e->prop.last;
     ps.n_rows = e->prop.rows_valid;
     const size_t cells = (size_t)ps.n_msgs * ps.n_nodes;
@@ -4104,6 +4157,7 @@ int gsx_prop_stats(gsx_engine* e, uint32_t* msg_hop_hist, uint32_t* node_receive
     if (!e) return GSX_EINVAL;
     auto& P = e->prop;
     if (!P.have_last) return fail(e, GSX_ESTATE, "no propagation call yet");
+    if (e->tprop.after) return fail(e, GSX_ESTATE, "the last propagation was a timed call (gsx_timed_results / gsx_timed_stats)");
     if (P.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
     gsx::PropState ps = P.last;
     ps.n_rows = P.rows_valid;
@@ -4153,6 +4207,329 @@ int gsx_prop_stats(gsx_engine* e, uint32_t* msg_hop_hist, uint32_t* node_receive
     }
     if (node_hop_sum && !sum_dev) {
         HIPCHK(e, hipMemcpyAsync(node_hop_sum, d_sum, 8 * N, hipMemcpyDeviceToHost, e->stream));
+        host = true;
+    }
+    if (host) HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GSX_OK;
+}
+
+// ---- timed propagation (gsx.h; gsx_prop_timed.hip) ---------------------------------
+
+int gsx_set_link_latency(gsx_engine* e, const uint8_t* ticks, size_t n_pairs) {
+    if (!e) return GSX_EINVAL;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    auto& T = e->tprop;
+    if (!ticks) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        if (T.lat) (void)hipFree(T.lat);
+        T.lat = nullptr;
+        T.max_lat = 0;
+        return GSX_OK;
+    }
+    if (n_pairs != e->E) return fail(e, GSX_EINVAL, "one latency per pair");
+    uint32_t mx = 0;
+    for (size_t q = 0; q < n_pairs; ++q) {
+        if (ticks[q] == 0) return fail(e, GSX_EINVAL, "a link latency of 0 ticks");
+        mx = std::max<uint32_t>(mx, ticks[q]);
+    }
+    if (!T.lat)
+        if (int rc = dalloc(e, &T.lat, std::max<size_t>(e->E, 1))) return rc;
+    HIPCHK(e, hipMemcpyAsync(T.lat, ticks, n_pairs, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    T.max_lat = mx;
+    return GSX_OK;
+}
+
+extern "C++" {
+namespace {
+template <typename U>
+int timed_grow(gsx_engine* e, U** p, size_t* cap, size_t want) {
+    if (*p && *cap >= want) return GSX_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    if (int rc = dalloc(e, p, std::max<size_t>(want, 1))) return rc;
+    *cap = want;
+    return GSX_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int gsx_propagate_timed(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_config* cfg, uint32_t max_ticks,
+                        gsx_timed_out* out) {
+    if (!e || !cfg || !out || (m && !msgs)) return GSX_EINVAL;
+    if (int rc = gx_busy(e)) return rc;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    if (e->sharded()) return fail(e, GSX_ESTATE, "timed propagation runs on unsharded engines only");
+    auto& P = e->prop;
+    auto& T = e->tprop;
+    if (P.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
+    if (e->gater.enforce) return fail(e, GSX_ESTATE, "timed propagation does not run under gsx_gater_enforce");
+    if (cfg->router != GSX_ROUTER_FLOODSUB && cfg->router != GSX_ROUTER_GOSSIPSUB)
+        return fail(e, GSX_EINVAL, "timed propagation: floodsub and gossipsub only");
+    const int64_t tick_ns = cfg->hop_latency_ns;
+    if (tick_ns <= 0 || cfg->validation_delay_ns < 0 || cfg->validation_delay_ns % tick_ns != 0 ||
+        cfg->credit_scores > GSX_CREDIT_DEFER || max_ticks > 65534 || m > 0xFFFFFFFFull)
+        return fail(e, GSX_EINVAL, "bad timed propagation config (tick length > 0, the validation delay a multiple of "
+                                   "it, max_ticks <= 65534)");
+    if (cfg->validation_delay_ns / tick_ns > 65534) return fail(e, GSX_ERANGE, "validation delay above 65534 ticks");
+    for (size_t k = 0; k < m; ++k) {
+        if (msgs[k].source >= e->n_total) return fail(e, GSX_ERANGE, "message source out of range");
+        if (msgs[k].validation > GSX_VALIDATION_THROTTLE) return fail(e, GSX_EINVAL, "bad message validation outcome");
+    }
+    if (e->n_nodes > gsx::PIN_NODE_MASK) return fail(e, GSX_ERANGE, "propagation needs < 2^28 nodes per engine");
+    if (!T.lat) return fail(e, GSX_ESTATE, "no link latencies (gsx_set_link_latency)");
+    const bool scored = cfg->topic < e->T && e->scored[cfg->topic];
+    if (cfg->credit_scores && scored && P.credit_pending && P.credit_topic != cfg->topic)
+        return fail(e, GSX_ESTATE, "deferred credits of another topic are pending: gsx_prop_fold_credits first");
+    // every score gate reads the scores of the call's start, all credits landed
+    if (int rc = fold_deferred(e)) return rc;
+    if (int rc = flush(e)) return rc;
+    if (cfg->router == GSX_ROUTER_GOSSIPSUB)
+        if (int rc = ensure_scores(e)) return rc;
+    const uint32_t W = prop_words(m);
+    const size_t N = e->n_nodes, E = e->E, orow = (N + 63) / 64;
+    const uint32_t vd = (uint32_t)(cfg->validation_delay_ns / tick_ns);
+    uint32_t R = 4;
+    while (R < T.max_lat + vd + 2) R <<= 1;
+    // every buffer of the call, before the tick loop
+    if (int rc = prop_pair_buffers(e)) return rc;  // (the pending credit counts)
+    {
+        int rc = 0;
+        if (!T.fwd) {
+            if ((rc = dalloc(e, &T.fwd, std::max<size_t>(E, 1))) || (rc = dalloc(e, &T.rfwd, std::max<size_t>(E, 1))) ||
+                (rc = dalloc(e, &T.pin, std::max<size_t>(E, 1))) || (rc = dalloc(e, &T.cent, std::max<size_t>(E, 1))) ||
+                (rc = dalloc(e, &T.cend, std::max<size_t>(N, 1))) || (rc = dalloc(e, &T.chg, 1)) ||
+                (rc = dalloc(e, &T.nchg, 1)) || (rc = dalloc(e, &T.ndirty, orow + 1)) ||
+                (rc = dalloc(e, &T.gray_pairs, 1)) || (rc = dalloc(e, &T.stats, (size_t)gsx::TS_WORDS)) ||
+                (rc = dalloc(e, &T.fcnt, std::max<size_t>(E, 1))) || (rc = dalloc(e, &T.dcnt, std::max<size_t>(E, 1))) ||
+                (rc = dalloc(e, &T.icnt, std::max<size_t>(E, 1))))
+                return rc;
+        }
+        size_t rocc_cap = T.occ_words, mark_cap = T.occ_words, seen_cap = T.row_words, orig_cap = T.row_words;
+        if ((rc = timed_grow(e, &T.ring, &T.ring_words, (size_t)R * N * W)) ||
+            (rc = timed_grow(e, &T.rocc, &rocc_cap, (size_t)R * orow)) ||
+            (rc = timed_grow(e, &T.mark, &mark_cap, (size_t)R * orow)) ||
+            (rc = timed_grow(e, &T.seen, &seen_cap, N * W)) || (rc = timed_grow(e, &T.origin, &orig_cap, N * W)) ||
+            (rc = timed_grow(e, &T.from, &T.from_words, E * W)) ||
+            (rc = timed_grow(e, &T.arr, &T.arr_cells, N * W * 64)) ||
+            (rc = timed_grow(e, &T.msgs, &T.msgs_cap, m)) || (rc = timed_grow(e, &T.vmask, &T.vmask_words, 2 * (size_t)W)))
+            return rc;
+        T.occ_words = std::min(rocc_cap, mark_cap);
+        T.row_words = std::min(seen_cap, orig_cap);
+        for (int i = 0; i < 2; ++i)
+            if (!T.ev[i]) HIPCHK(e, hipEventCreate(&T.ev[i]));
+    }
+    if (int rc = fanout_publish(e, msgs, m, cfg)) return rc;
+    bool has_drop = false;
+    {
+        std::vector<uint64_t> vm(2 * (size_t)W, 0);
+        std::vector<gsx::DevMsg> hm(m);
+        for (size_t k = 0; k < m; ++k) {
+            hm[k] = gsx::DevMsg{msgs[k].source, msgs[k].validation, msgs[k].msg_id};
+            if (msgs[k].validation != GSX_VALIDATION_ACCEPT) {
+                vm[k / 64] |= 1ull << (k % 64);
+                if (msgs[k].validation == GSX_VALIDATION_REJECT) vm[W + k / 64] |= 1ull << (k % 64);
+                has_drop = true;
+            }
+        }
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        HIPCHK(e, hipMemcpy(T.vmask, vm.data(), 16 * (size_t)W, hipMemcpyHostToDevice));
+        if (m) HIPCHK(e, hipMemcpy(T.msgs, hm.data(), sizeof(gsx::DevMsg) * m, hipMemcpyHostToDevice));
+    }
+    gsx::PropState ps = prop_state(e, W, m, cfg);
+    ps.fwd = T.fwd;
+    ps.rfwd = T.rfwd;
+    ps.pin = T.pin;
+    ps.cent = T.cent;
+    ps.cend = T.cend;
+    ps.chg = T.chg;
+    ps.nchg = T.nchg;
+    ps.ndirty = T.ndirty;
+    ps.chg_cap = 1;
+    ps.inc = 0;
+    ps.gray_pairs = T.gray_pairs;
+    ps.gdec = nullptr;
+    ps.msgs = T.msgs;
+    ps.drop = has_drop ? T.vmask : nullptr;
+    ps.reject = T.vmask + W;
+    ps.from_mask = T.from;
+    ps.seen = T.seen;
+    ps.origin = T.origin;
+    ps.invcnt = P.inv;
+    gsx::TimedState ts{};
+    ts.ring = T.ring;
+    ts.rocc = T.rocc;
+    ts.mark = T.mark;
+    ts.seen = T.seen;
+    ts.origin = T.origin;
+    ts.from = T.from;
+    ts.arr = T.arr;
+    ts.lat = T.lat;
+    ts.fcnt = T.fcnt;
+    ts.dcnt = T.dcnt;
+    ts.icnt = T.icnt;
+    ts.stats = T.stats;
+    ts.R = R;
+    ts.vd = vd;
+    ts.max_ticks = max_ticks;
+    {
+        const int64_t win = ps.window < 0 ? -1 : ps.window / tick_ns;  // floor(window / tick); a negative window: none inside
+        const int64_t lim = win < 0 ? -1 : (int64_t)vd + win;
+        ts.lim = lim < 0 ? 0u : (uint32_t)std::min<int64_t>(lim, 0xFFFFFFFFll);
+    }
+    std::memset(out, 0, sizeof(*out));
+    T.ps = ps;
+    T.ts = ts;
+    T.have = true;
+    T.after = true;
+    if (!P.have_last) P.last = ps;  // (gsx_prop_fold_credits folds with the last call's state)
+    hipStream_t st = e->stream;
+    HIPCHK(e, hipMemsetAsync(T.ring, 0, 8 * N * W, st));  // slot 0: the sources' rows
+    HIPCHK(e, hipMemsetAsync(T.rocc, 0, 8 * (size_t)R * orow, st));
+    HIPCHK(e, hipMemsetAsync(T.mark, 0, 8 * (size_t)R * orow, st));
+    HIPCHK(e, hipMemsetAsync(T.seen, 0, 8 * N * W, st));
+    HIPCHK(e, hipMemsetAsync(T.origin, 0, 8 * N * W, st));
+    HIPCHK(e, hipMemsetAsync(T.from, 0, 8 * E * W, st));
+    HIPCHK(e, hipMemsetAsync(T.arr, 0xFF, 2 * N * W * 64, st));
+    HIPCHK(e, hipMemsetAsync(T.fcnt, 0, 4 * std::max<size_t>(E, 1), st));
+    HIPCHK(e, hipMemsetAsync(T.dcnt, 0, 4 * std::max<size_t>(E, 1), st));
+    HIPCHK(e, hipMemsetAsync(T.icnt, 0, 4 * std::max<size_t>(E, 1), st));
+    HIPCHK(e, hipMemsetAsync(T.stats, 0, 8 * (size_t)gsx::TS_WORDS, st));
+    HIPCHK(e, hipMemsetAsync(T.gray_pairs, 0, 8, st));
+    HIPCHK(e, hipMemsetAsync(T.nchg, 0, 4, st));
+    HIPCHK(e, hipMemsetAsync(T.ndirty, 0, 8 * (orow + 1), st));
+    if (m == 0 || N == 0) {
+        HIPCHK(e, hipStreamSynchronize(st));
+        return GSX_OK;
+    }
+    HIPCHK(e, gsx::launch_prop_fwd(ps, dev_state(e), st));  // fwd bytes, pins, compacted senders: gsx_propagate's
+    HIPCHK(e, gsx::launch_timed_init(ps, ts, st));
+    HIPCHK(e, hipEventRecord(T.ev[0], st));
+    uint32_t launches = 1, t = 0;
+    HIPCHK(e, gsx::launch_timed_tick(ps, ts, 0, st));
+    unsigned long long last_copy = 0;
+    // every tick up to the last arrival known so far runs; the device's count of
+    // that tick is read back once per batch of them
+    for (;;) {
+        HIPCHK(e, hipMemcpyAsync(&last_copy, T.stats + gsx::TS_LAST_COPY, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        if (last_copy <= t) break;
+        while (t < last_copy) {
+            HIPCHK(e, gsx::launch_timed_tick(ps, ts, ++t, st));
+            ++launches;
+        }
+    }
+    HIPCHK(e, hipEventRecord(T.ev[1], st));
+    if (ps.credit) {
+        HIPCHK(e, gsx::launch_timed_add(P.first, T.fcnt, E, st));
+        HIPCHK(e, gsx::launch_timed_add(P.dup, T.dcnt, E, st));
+        HIPCHK(e, gsx::launch_timed_add(P.inv, T.icnt, E, st));
+        P.credit_pending = true;
+        P.credit_topic = cfg->topic;
+        if (cfg->credit_scores == GSX_CREDIT_NOW)
+            if (int rc = prop_fold(e, ps)) return rc;
+    }
+    unsigned long long sv[gsx::TS_WORDS];
+    HIPCHK(e, hipMemcpyAsync(sv, T.stats, sizeof(sv), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    out->deliveries = sv[gsx::TS_DELIV];
+    out->duplicates = sv[gsx::TS_DUPS];
+    out->dup_in_window = sv[gsx::TS_DUPS_IN];
+    out->rejected = sv[gsx::TS_REJ];
+    out->ignored = sv[gsx::TS_IGN];
+    out->graylisted = sv[gsx::TS_GRAY];
+    out->transmissions = out->deliveries + out->duplicates + out->rejected + out->ignored + out->graylisted;
+    out->last_tick = (uint32_t)sv[gsx::TS_LAST_TICK];
+    out->ticks_run = t;
+    out->launches = launches;
+    out->marked_nodes = sv[gsx::TS_MARKED];
+    float ms = 0;
+    HIPCHK(e, hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
+    out->kernel_ms = ms;
+    return GSX_OK;
+}
+
+int gsx_timed_results(gsx_engine* e, uint16_t* tick, int32_t* first_from) {
+    if (!e) return GSX_EINVAL;
+    auto& T = e->tprop;
+    if (!T.have) return fail(e, GSX_ESTATE, "no gsx_propagate_timed call yet");
+    const gsx::PropState& ps = T.ps;
+    const size_t cells = (size_t)ps.n_msgs * ps.n_nodes;
+    if (cells == 0) return GSX_OK;
+    if (tick) {
+        uint16_t* d = nullptr;
+        if (int rc = dalloc(e, &d, cells)) return rc;
+        HIPCHK(e, gsx::launch_timed_export(ps, T.ts, d, e->stream));
+        HIPCHK(e, hipMemcpyAsync(tick, d, 2 * cells, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        (void)hipFree(d);
+    }
+    if (first_from) {
+        int32_t* d = nullptr;
+        if (int rc = dalloc(e, &d, cells)) return rc;
+        HIPCHK(e, hipMemsetAsync(d, 0xFF, 4 * cells, e->stream));
+        HIPCHK(e, gsx::launch_prop_from(ps, d, e->stream));
+        HIPCHK(e, hipMemcpyAsync(first_from, d, 4 * cells, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        (void)hipFree(d);
+    }
+    return GSX_OK;
+}
+
+int gsx_timed_stats(gsx_engine* e, uint32_t bin_ticks, uint32_t n_bins, uint32_t* msg_tick_hist,
+                    uint32_t* node_received, uint64_t* node_tick_sum) {
+    if (!e) return GSX_EINVAL;
+    auto& T = e->tprop;
+    if (!T.have) return fail(e, GSX_ESTATE, "no gsx_propagate_timed call yet");
+    if (bin_ticks == 0 || n_bins == 0 || n_bins > 1024) return fail(e, GSX_EINVAL, "bin_ticks >= 1, 1 <= n_bins <= 1024");
+    const gsx::PropState& ps = T.ps;
+    const size_t m = ps.n_msgs, N = ps.n_nodes;
+    if (m == 0 || N == 0 || (!msg_tick_hist && !node_received && !node_tick_sum)) return GSX_OK;
+    const size_t cells = m * n_bins;
+    // device memory is written in place, in stream order; host memory gets a copy of the engine's buffers
+    const bool hist_dev = msg_tick_hist && on_device(msg_tick_hist);
+    const bool recv_dev = node_received && on_device(node_received);
+    const bool sum_dev = node_tick_sum && on_device(node_tick_sum);
+    if (msg_tick_hist && !hist_dev && T.st_hist_cap < cells) {
+        if (T.st_hist) {
+            HIPCHK(e, hipStreamSynchronize(e->stream));
+            (void)hipFree(T.st_hist);
+        }
+        T.st_hist = nullptr;
+        T.st_hist_cap = 0;
+        if (int rc = dalloc(e, &T.st_hist, cells)) return rc;
+        T.st_hist_cap = cells;
+    }
+    if (node_received && !recv_dev && !T.st_recv)
+        if (int rc = dalloc(e, &T.st_recv, N)) return rc;
+    if (node_tick_sum && !sum_dev && !T.st_sum)
+        if (int rc = dalloc(e, &T.st_sum, N)) return rc;
+    uint32_t* d_hist = !msg_tick_hist ? nullptr : hist_dev ? msg_tick_hist : T.st_hist;
+    uint32_t* d_recv = !node_received ? nullptr : recv_dev ? node_received : T.st_recv;
+    unsigned long long* d_sum =
+        !node_tick_sum ? nullptr : sum_dev ? reinterpret_cast<unsigned long long*>(node_tick_sum) : T.st_sum;
+    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
+    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    if (d_hist) HIPCHK(e, hipMemsetAsync(d_hist, 0, 4 * cells, e->stream));
+    if (d_recv) HIPCHK(e, hipMemsetAsync(d_recv, 0, 4 * N, e->stream));
+    if (d_sum) HIPCHK(e, hipMemsetAsync(d_sum, 0, 8 * N, e->stream));
+    HIPCHK(e, gsx::launch_timed_stats(ps, T.ts, bin_ticks, n_bins, d_hist, d_recv, d_sum, e->stream));
+    if (region) {
+        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
+        ++e->t_used;
+    }
+    bool host = false;
+    if (msg_tick_hist && !hist_dev) {
+        HIPCHK(e, hipMemcpyAsync(msg_tick_hist, d_hist, 4 * cells, hipMemcpyDeviceToHost, e->stream));
+        host = true;
+    }
+    if (node_received && !recv_dev) {
+        HIPCHK(e, hipMemcpyAsync(node_received, d_recv, 4 * N, hipMemcpyDeviceToHost, e->stream));
+        host = true;
+    }
+    if (node_tick_sum && !sum_dev) {
+        HIPCHK(e, hipMemcpyAsync(node_tick_sum, d_sum, 8 * N, hipMemcpyDeviceToHost, e->stream));
         host = true;
     }
     if (host) HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -4509,6 +4886,7 @@ int gsx_gater_fold_prop(gsx_engine* e) {
     auto& P = e->prop;
     if (!G.on) return fail(e, GSX_ESTATE, "no gater (gsx_set_gater_params)");
     if (!P.have_last) return fail(e, GSX_ESTATE, "no propagation call yet");
+    if (e->tprop.after) return fail(e, GSX_ESTATE, "the last propagation was a timed call (gsx_timed_results / gsx_timed_stats)");
     if (P.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
     if (e->sharded()) return fail(e, GSX_ESTATE, "the gater folds propagations of unsharded engines only");
     gsx::PropState ps = P.last;
@@ -4801,6 +5179,7 @@ int gsx_tag_fold_prop(gsx_engine* e) {
     auto& P = e->prop;
     if (int rc = tag_on(e)) return rc;
     if (!P.have_last) return fail(e, GSX_ESTATE, "no propagation call yet");
+    if (e->tprop.after) return fail(e, GSX_ESTATE, "the last propagation was a timed call (gsx_timed_results / gsx_timed_stats)");
     if (P.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
     if (e->sharded()) return fail(e, GSX_ESTATE, "the tag tracer folds propagations of unsharded engines only");
     gsx::PropState ps = P.last;
@@ -4913,6 +5292,7 @@ int gsx_conn_trim(gsx_engine* e, uint32_t low_water, uint8_t* trim, uint32_t* no
 int gsx_prop_duplicates(gsx_engine* e, uint64_t* rows, size_t n_words) {
     if (!e || !rows) return GSX_EINVAL;
     if (!e->prop.have_last) return fail(e, GSX_ESTATE, "no gsx_propagate call yet");
+    if (e->tprop.after) return fail(e, GSX_ESTATE, "the last propagation was a timed call (gsx_timed_results / gsx_timed_stats)");
     if (e->prop.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
     if (e->sharded()) return fail(e, GSX_EINVAL, "duplicate rows are exported by unsharded engines only");
     gsx::PropState ps = e->prop.last;

@@ -282,6 +282,29 @@ class PropOut(C.Structure):
                     rejected=self.rejected, ignored=self.ignored, graylisted=self.graylisted)
 
 
+class TimedOut(C.Structure):
+    """gsx_timed_out"""
+    _fields_ = [
+        ("deliveries", C.c_uint64),
+        ("duplicates", C.c_uint64),
+        ("transmissions", C.c_uint64),
+        ("rejected", C.c_uint64),
+        ("ignored", C.c_uint64),
+        ("graylisted", C.c_uint64),
+        ("dup_in_window", C.c_uint64),
+        ("last_tick", C.c_uint32),
+        ("ticks_run", C.c_uint32),
+        ("launches", C.c_uint32),
+        ("kernel_ms", C.c_double),
+        ("marked_nodes", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        return dict(deliveries=self.deliveries, duplicates=self.duplicates, transmissions=self.transmissions,
+                    rejected=self.rejected, ignored=self.ignored, graylisted=self.graylisted,
+                    dup_in_window=self.dup_in_window, last_tick=self.last_tick, ticks_run=self.ticks_run)
+
+
 class Msg(C.Structure):
     _fields_ = [("source", C.c_uint32), ("validation", C.c_uint32), ("msg_id", C.c_uint64)]
 
@@ -575,6 +598,11 @@ SIGNATURES = {
     "gsx_prop_results": (C.c_int, [C.c_void_p, P(C.c_uint8), P(C.c_int32)]),
     # (host or device pointers, like gsx_prop_pending_credits: passed as addresses)
     "gsx_prop_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsx_set_link_latency": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_size_t]),
+    "gsx_propagate_timed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, P(PropConfig), C.c_uint32, P(TimedOut)]),
+    "gsx_timed_results": (C.c_int, [C.c_void_p, P(C.c_uint16), P(C.c_int32)]),
+    # (host or device pointers, like gsx_prop_stats: passed as addresses)
+    "gsx_timed_stats": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsx_score_stats_edges": (C.c_int, [C.c_void_p, P(ScoreStatsSpec)]),
     "gsx_score_stats": (C.c_int, [C.c_void_p, P(ScoreStatsSpec), P(ScoreStatsOut)]),
     "gsx_prop_set_tracking": (C.c_int, [C.c_void_p, C.c_uint32]),

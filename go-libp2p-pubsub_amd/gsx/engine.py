@@ -118,6 +118,80 @@ class PropStats:
                          sum(p.node_hop_sum for p in parts) if per_node else None)
 
 
+class TimedStats:
+    """Per-message arrival-time summary of a timed propagation (gsx_timed_stats):
+    tick_hist[k, b] = nodes whose arrival tick a of message k has min(a // bin_ticks,
+    n_bins - 1) == b (the source, tick 0, in bin 0); optionally node_received[u] =
+    messages node u got at ticks >= 1 and node_tick_sum[u] = the sum of those ticks.
+    tick_ns (the call's tick length) turns ticks into milliseconds.  Numpy on those
+    integers; nothing here touches the device."""
+
+    def __init__(self, tick_hist, bin_ticks, node_received=None, node_tick_sum=None, tick_ns=None):
+        self.tick_hist = np.ascontiguousarray(tick_hist, dtype=np.uint32)
+        if self.tick_hist.ndim != 2:
+            raise ValueError("tick_hist is [messages, bins]")
+        self.bin_ticks = int(bin_ticks)
+        self.node_received = None if node_received is None else np.ascontiguousarray(node_received, dtype=np.uint32)
+        self.node_tick_sum = None if node_tick_sum is None else np.ascontiguousarray(node_tick_sum, dtype=np.uint64)
+        self.tick_ns = tick_ns
+
+    @property
+    def n_msgs(self) -> int:
+        return self.tick_hist.shape[0]
+
+    @property
+    def n_bins(self) -> int:
+        return self.tick_hist.shape[1]
+
+    def _h(self) -> np.ndarray:
+        return self.tick_hist.astype(np.int64)
+
+    def reached(self) -> np.ndarray:
+        """[m] i64: nodes that hold each message, its source not counted."""
+        return self._h().sum(1) - 1
+
+    def delivery_ratio(self, n_receivers) -> np.ndarray:
+        """[m] f64: reached() / n_receivers."""
+        return self.reached() / np.asarray(n_receivers, dtype=np.float64)
+
+    def last_bin(self) -> np.ndarray:
+        """[m] i64: the last bin with a node in it (-1: an empty row)."""
+        nz = self.tick_hist != 0
+        last = nz.shape[1] - 1 - np.argmax(nz[:, ::-1], axis=1)
+        return np.where(nz.any(1), last, -1).astype(np.int64)
+
+    def ticks_to_fraction(self, q: float, n_receivers) -> np.ndarray:
+        """[m] i64: the end tick (exclusive) of the first bin after which at least a fraction q of
+        n_receivers holds the message, i.e. an upper bound of the time to q at the bins' resolution
+        (exact with bin_ticks = 1: the tick itself + 1); -1 if the call never got there, or only in
+        the open last bin."""
+        cum = np.cumsum(self._h(), axis=1) - 1  # the source is not a receipt
+        ok = cum / np.asarray(n_receivers, dtype=np.float64).reshape(-1, 1) >= q
+        b = np.argmax(ok, axis=1)
+        good = ok.any(1) & ((b < self.n_bins - 1) | (self.n_bins == 1))
+        return np.where(good, (b + 1) * self.bin_ticks, -1).astype(np.int64)
+
+    def ms(self, ticks) -> np.ndarray:
+        """ticks -> milliseconds (needs tick_ns); negative (never) stays negative."""
+        t = np.asarray(ticks, dtype=np.float64)
+        return np.where(t >= 0, t * (self.tick_ns / 1e6), -1.0)
+
+    def node_mean_tick(self) -> np.ndarray:
+        """[n] f64: mean arrival tick per node (nan: the node received nothing); needs per_node."""
+        r = self.node_received.astype(np.float64)
+        return np.where(r > 0, self.node_tick_sum.astype(np.float64) / np.maximum(r, 1), np.nan)
+
+    def __add__(self, other: "TimedStats") -> "TimedStats":
+        """Two calls over the same nodes and bins (e.g. two message batches): the rows follow one
+        another, the per-node arrays (kept when both sides have them) add up."""
+        if self.n_bins != other.n_bins or self.bin_ticks != other.bin_ticks:
+            raise ValueError("histograms of different bins")
+        both = self.node_received is not None and other.node_received is not None
+        return TimedStats(np.concatenate([self.tick_hist, other.tick_hist], 0), self.bin_ticks,
+                          self.node_received.astype(np.uint64) + other.node_received if both else None,
+                          self.node_tick_sum + other.node_tick_sum if both else None, self.tick_ns)
+
+
 class ScoreStats:
     """Threshold standings of the scores (gsx_score_stats): the selected pairs
     per score bin, bin(s) = the edges k with not s < edges[k] (a NaN score: the
@@ -376,6 +450,60 @@ class Engine:
         return out, hop, frm
 
     _track = True
+
+    # -- timed propagation (gsx.h: gsx_propagate_timed) ------------------------------------
+    def set_link_latency(self, ticks):
+        """gsx_set_link_latency: [n_pairs] ticks 1 .. 255 per pair (u -> v), the time a copy sent
+        by v takes to reach u; None removes them."""
+        if ticks is None:
+            self._chk(self.lib.gsx_set_link_latency(self.h, None, 0), "gsx_set_link_latency")
+            return
+        t = np.ascontiguousarray(ticks)
+        if t.size and (t.min() < 0 or t.max() > 255):
+            raise ValueError("latencies are 1 .. 255 ticks")
+        t = t.astype(np.uint8)
+        self._chk(self.lib.gsx_set_link_latency(self.h, _ptr(t, C.c_uint8), len(t)), "gsx_set_link_latency")
+
+    def propagate_timed(self, msgs, cfg: abi.PropConfig, max_ticks: int, want_results: bool = False):
+        """gsx_propagate_timed (cfg.hop_latency_ns: the tick length) -> (TimedOut, tick [m, n] u16
+        or None, first_from [m, n] i32 or None)"""
+        ms = np.ascontiguousarray(msgs, dtype=abi.msg_dtype())
+        out = abi.TimedOut()
+        self._chk(self.lib.gsx_propagate_timed(self.h, ms.ctypes.data_as(C.c_void_p), len(ms), C.byref(cfg),
+                                               int(max_ticks), C.byref(out)), "gsx_propagate_timed")
+        self._tick_ns = int(cfg.hop_latency_ns)
+        tick = frm = None
+        if want_results:
+            tick, frm = self.timed_results(len(ms))
+        return out, tick, frm
+
+    def timed_results(self, n_msgs: int):
+        """-> (tick [m, n] u16, first_from [m, n] i32) of the last timed call."""
+        tick = np.empty((n_msgs, self.n_nodes), dtype=np.uint16)
+        frm = np.empty((n_msgs, self.n_nodes), dtype=np.int32)
+        self._chk(self.lib.gsx_timed_results(self.h, _ptr(tick, C.c_uint16), _ptr(frm, C.c_int32)), "gsx_timed_results")
+        return tick, frm
+
+    def timed_stats(self, n_msgs: int, bin_ticks: int, n_bins: int, per_node: bool = False, out_ptrs=None):
+        """gsx_timed_stats of the last timed call (n_msgs: its messages) -> TimedStats: tick_hist
+        [m, n_bins] u32 and, with per_node, node_received [n] u32 and node_tick_sum [n] u64.
+
+        out_ptrs = (hist, received, tick_sum): device pointers or tensors (None / 0 skips one)
+        written in stream order with no host sync, as prop_stats takes them; then -> None."""
+        if out_ptrs is not None:
+            self._chk(self.lib.gsx_timed_stats(self.h, int(bin_ticks), int(n_bins),
+                                               *[self._p(p) if p is not None else None for p in out_ptrs]),
+                      "gsx_timed_stats")
+            return None
+        hist = np.zeros((n_msgs, n_bins), dtype=np.uint32)
+        recv = np.zeros(self.n_nodes, dtype=np.uint32) if per_node else None
+        tsum = np.zeros(self.n_nodes, dtype=np.uint64) if per_node else None
+        self._chk(self.lib.gsx_timed_stats(self.h, int(bin_ticks), int(n_bins),
+                                           C.c_void_p(hist.ctypes.data if hist.size else None),
+                                           C.c_void_p(recv.ctypes.data if per_node and recv.size else None),
+                                           C.c_void_p(tsum.ctypes.data if per_node and tsum.size else None)),
+                  "gsx_timed_stats")
+        return TimedStats(hist, bin_ticks, recv, tsum, getattr(self, "_tick_ns", None))
 
     def prop_duplicates(self, n_msgs: int) -> np.ndarray:
         """gsx_prop_duplicates: [n_pairs, ceil(m / 64)] u64, bit m of row q = the

@@ -25,6 +25,7 @@ TAG_STATE = 4
 TAG_IP = 5
 TAG_EVENT = 6
 TAG_VICTIM = 9
+TAG_LAT = 15  # link latencies (link_latency)
 
 
 def _mix(z: np.ndarray) -> np.ndarray:
@@ -308,3 +309,15 @@ def synthetic_state(ov: Overlay, n_topics: int, now_ns: int, seed: int = SEED, p
     st["behaviour_penalty"] = uniform(seed, TAG_STATE, p, 10) * 5.0
     st["last_refresh_ns"] = now_ns  # meshTime above is what a refresh at `now` wrote
     return st
+
+
+def link_latency(ov, seed: int, lo: int, hi: int, symmetric: bool = True) -> np.ndarray:
+    """[n_pairs] u8 ticks per pair (u -> v) for Engine.set_link_latency: lo + h(seed, TAG_LAT, a, b)
+    mod (hi - lo + 1) with (a, b) = (min(u, v), max(u, v)), the same for both directions of a
+    link, or (u, v) when not symmetric.  1 <= lo <= hi <= 255."""
+    if not 1 <= lo <= hi <= 255:
+        raise ValueError("latencies are 1 .. 255 ticks")
+    u = ov.pair_observer().astype(np.uint64)
+    v = np.asarray(ov.col).astype(np.uint64)
+    a, b = (np.minimum(u, v), np.maximum(u, v)) if symmetric else (u, v)
+    return (np.uint64(lo) + h(seed, TAG_LAT, a, b) % np.uint64(hi - lo + 1)).astype(np.uint8)

@@ -642,6 +642,83 @@ int gsx_prop_replace_pending_invalid(gsx_engine* e, const uint32_t* inv);
  * replace the pending counts before folding. */
 int gsx_prop_fold_credits(gsx_engine* e, const uint32_t* first, const uint32_t* dup);
 
+/* ---- timed propagation: a latency per directed link, arrival times in ticks ---- */
+/* gsx_propagate's rule on a tick clock.  Time is an integer tick of
+ * cfg->hop_latency_ns nanoseconds (the tick length, > 0; cfg->max_hops is
+ * ignored).  Pair q = (u -> v) carries lat[q] in 1 .. 255: the ticks a copy
+ * sent by v takes to reach u (one uint8_t per pair; the two directions of a
+ * link may differ).
+ *   - the source holds message m at tick 0 and sends at tick 0 (a local
+ *     publish validates synchronously);
+ *   - a node that first receives m at tick a finishes validating at a + vd,
+ *     vd = validation_delay_ns / tick length (a multiple of it), and sends
+ *     then, to exactly the targets gsx_propagate's eligibility lets through
+ *     (FORWARD for received messages, PUBLISH for own ones; scores as they
+ *     stand when the call starts), never to the peer it first got m from,
+ *     never to m's origin.  A copy v sends at tick f reaches u at
+ *     f + lat[(u -> v)];
+ *   - u's first receipt of m is the copy of the smallest arrival tick, among
+ *     copies of one tick the lowest-indexed sender's; every other copy that
+ *     reaches u and is not dropped is a duplicate;
+ *   - AcceptFrom (gossipsub) drops a graylisted sender's copies before
+ *     pushMsg: not seen, not duplicates, counted in `graylisted`;
+ *   - a message whose validation is not ACCEPT travels one link from its
+ *     source: its receivers mark it seen and do not forward it; REJECT adds
+ *     one P4 count to the receiver's record of the sender;
+ *   - the first deliverer's pair gets a first receipt (fmd, and mmd if in
+ *     mesh); a duplicate arriving at tick d at a node whose first copy arrived
+ *     at tick a is inside the P3 window iff
+ *     d - a <= vd + floor(MeshMessageDeliveriesWindow / tick length), i.e.
+ *     arrival <= validated + window (copies that arrive during validation are
+ *     inside; score.go:944-974).  GSX_CREDIT_OFF / NOW / DEFER, the pending
+ *     counts and their fold are gsx_propagate's;
+ *   - the call ends at max_ticks (<= 65534) or when no copy is in flight;
+ *     copies still in flight at max_ticks are not counted anywhere.
+ * With every lat[q] = l the call equals gsx_propagate with hop_latency_ns =
+ * l ticks bit for bit: a node reached at hop h >= 1 is reached at tick
+ * h l + (h - 1) vd from the same first deliverer, and every counter, state
+ * field and score is equal.  All integer work: bit-identical from run to run.
+ *
+ * Refused (the engine is left unchanged): RandomSub (GSX_EINVAL), range
+ * shards, a stepped call in flight, gsx_gater_enforce on, no latencies set
+ * (GSX_ESTATE); a delay that is no multiple of the tick, max_ticks > 65534
+ * (GSX_EINVAL).  A timed call does not enter the message cache and feeds
+ * neither the gossip exchange nor gsx_gater_fold_prop / gsx_tag_fold_prop;
+ * after it, those two, gsx_prop_results, gsx_prop_stats and
+ * gsx_prop_duplicates return GSX_ESTATE until the next gsx_propagate (its rows
+ * are not theirs).  A publisher that has not joined the topic gets its
+ * fanout as in gsx_propagate. */
+/* ticks[n_pairs] (host memory), every entry 1 .. 255 (a 0: GSX_EINVAL);
+ * NULL removes the latencies.  Loading an overlay removes them too. */
+int gsx_set_link_latency(gsx_engine* e, const uint8_t* ticks, size_t n_pairs);
+typedef struct gsx_timed_out {
+    uint64_t deliveries, duplicates, transmissions, rejected, ignored, graylisted; /* as gsx_prop_out */
+    uint64_t dup_in_window;  /* duplicates inside the P3 window */
+    uint32_t last_tick;      /* last tick with a first receipt (accepted or not) */
+    uint32_t ticks_run;      /* the last tick a copy arrived at (graylisted copies too): the ticks run */
+    uint32_t launches;       /* tick launches (tick 0 included) */
+    double kernel_ms;        /* device time from the first to the last tick launch (HIP events) */
+    uint64_t marked_nodes;   /* (node, tick) pairs with an arriving copy: what the tick launches walked */
+} gsx_timed_out;
+int gsx_propagate_timed(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_prop_config* cfg,
+                        uint32_t max_ticks, gsx_timed_out* out);
+/* Arrival tick (0xFFFF = never, 0 at the source) and first deliverer (global
+ * id, -1 = none) of the last timed call, [message][node], host memory; either
+ * pointer may be NULL. */
+int gsx_timed_results(gsx_engine* e, uint16_t* tick, int32_t* first_from);
+/* The timed twin of gsx_prop_stats, reduced on the device from the arrival
+ * ticks with integer adds only (bit-identical from run to run).  With a(k, u)
+ * the tick gsx_timed_results writes:
+ *   msg_tick_hist[k * n_bins + b]  nodes u with a(k, u) != 0xFFFF and
+ *                     min(a(k, u) / bin_ticks, n_bins - 1) == b (the source,
+ *                     tick 0, included; 1 <= n_bins <= 1024, bin_ticks >= 1),
+ *   node_received[u]  messages k with 1 <= a(k, u) < 0xFFFF,
+ *   node_tick_sum[u]  the sum of a(k, u) over those messages.
+ * Pointer rules as gsx_prop_stats: host or device memory, NULL skips an
+ * output, device outputs are written in stream order with no host sync. */
+int gsx_timed_stats(gsx_engine* e, uint32_t bin_ticks, uint32_t n_bins, uint32_t* msg_tick_hist,
+                    uint32_t* node_received, uint64_t* node_tick_sum);
+
 /* Orders the engine's work on a caller's HIP stream (hipStream_t; NULL = the
  * engine's own), e.g. torch's current stream, so that its kernels and the
  * caller's RCCL collectives on the same device are stream-ordered. */
