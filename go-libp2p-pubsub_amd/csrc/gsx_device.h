@@ -110,9 +110,9 @@ struct DevState {
     uint8_t* rflags;      // tiled record flags
     uint8_t* zmap;        // per (tile, topic, MFP | IMD): ZM_ZERO / ZM_MAYBE
     uint8_t* pzmap;       // per (tile, PZ_APP | PZ_P6): ZM_ZERO / ZM_MAYBE
-    uint8_t* pflags;      // per pair: PRESENT | CONNECTED
+    uint8_t* pflags;      // per pair: PRESENT | CONNECTED | write-back epoch of bp (2 bits)
     int64_t* expire;      // per pair: retention expiry
-    double* bp;           // per pair: behaviourPenalty
+    double* bp;           // per pair: behaviourPenalty (as of its epoch: bp_read, gsx_ops.h)
     double* app;          // per pair: AppSpecificScore snapshot (GSX_EV_APP_SCORE updates one)
     const uint32_t* ipg;  // 2 per pair: (observer, ip) group id | WL bit, or NONE
     uint32_t* ipcount;    // per group: number of present pairs carrying it
@@ -127,6 +127,7 @@ struct DevState {
     uint32_t phase;
     uint32_t wb_period;
     double decay_to_zero;
+    double d7;  // BehaviourPenaltyDecay (the pending decays of bp, PAIR_EPOCH below)
 };
 
 constexpr uint8_t REC_IN_MESH = 0x01;
@@ -141,6 +142,13 @@ constexpr uint8_t REC_EPOCH = 0x18;
 constexpr int REC_EPOCH_SHIFT = 3;
 constexpr uint8_t PAIR_PRESENT = 0x01;
 constexpr uint8_t PAIR_CONNECTED = 0x02;
+// The write-back epoch of a pair's behaviour penalty, by REC_EPOCH's rules: a
+// connected pair's stored bp is its value as of the refresh at which
+// DevState::phase was this value, and (phase - epoch) & 3 decays of d7 pend
+// (bp_pend, gsx_ops.h).  A retained pair is never decayed: nothing pends there.
+// Every reader of the flag byte tests bits, never the whole byte.
+constexpr uint8_t PAIR_EPOCH = 0x0C;
+constexpr int PAIR_EPOCH_SHIFT = 2;
 constexpr uint32_t IPG_NONE = 0xFFFFFFFFu;
 constexpr uint32_t IPG_WL = 0x80000000u;  // whitelisted IP: counted, never penalised
 
@@ -1098,6 +1106,9 @@ hipError_t launch_recap(const DevState& s, uint32_t topic, double cap2, double c
 // Applies every record's pending decays, stores the counters and clears every
 // epoch; the caller then sets phase = 0.
 hipError_t launch_materialize(const DevState& s, hipStream_t st);
+// Export of the per-pair state that carries an epoch: pflags[p] without
+// PAIR_EPOCH and / or bp[p] with its pending decays (either may be null).
+hipError_t launch_pair_export(const DevState& s, uint8_t* pflags, double* bp, hipStream_t st);
 // The drop-in round trip (k_dropin): events + score() of the pairs they change
 // (prs; the whole row of the observers in obs: AddPeer / RemovePeer move their
 // IP colocation counts) into the device vector and the host-mapped copy, then

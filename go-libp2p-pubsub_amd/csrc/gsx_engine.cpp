@@ -86,6 +86,13 @@ struct gsx_engine {
     // refreshes since the last one that did (DevState::phase, REC_EPOCH).
     uint32_t phase = 0;
     uint32_t wb_period = 4;
+    // gsx_refresh launches the purge only while a retained pair (present, not
+    // connected) can exist.  retain_horizon bounds `expire` of every such pair
+    // from above (kRetainUnknown: no bound, always launch); the sites that make
+    // one raise it (note_retained).  Host-side only: nothing is read back.
+    bool retained_possible = false;
+    int64_t retain_horizon = INT64_MIN;
+    uint64_t purge_launches = 0;  // since the overlay was loaded
     std::vector<int64_t> row_ptr;
     std::vector<int32_t> col_host;
     std::vector<uint32_t> pair_obs;
@@ -687,7 +694,24 @@ gsx::DevState dev_state(const gsx_engine* e) {
     s.phase = e->phase;
     s.wb_period = e->wb_period;
     s.decay_to_zero = e->pp.decay_to_zero;
+    s.d7 = e->pp.behaviour_penalty_decay;
     return s;
+}
+
+// A retained pair may exist whose expiry is at most `bound` (kRetainUnknown:
+// no bound can be given).
+constexpr int64_t kRetainUnknown = INT64_MAX;
+void note_retained(gsx_engine* e, int64_t bound) {
+    e->retained_possible = true;
+    e->retain_horizon = std::max(e->retain_horizon, bound);
+}
+// The RemovePeer events about to be applied under the current peer parameters
+// (gsx_set_peer_params flushes first, so these are the ones the device uses):
+// ev_remove_peer sets expire = now + retain_ns, with the same wrapping sum.
+void note_retained_events(gsx_engine* e, const std::vector<gsx_event>& evs) {
+    for (const gsx_event& x : evs)
+        if (x.kind == GSX_EV_REMOVE_PEER)
+            note_retained(e, (int64_t)((uint64_t)x.now_ns + (uint64_t)e->pp.retain_score_ns));
 }
 
 // PZ_P6 of the whole pair zero map marked: with any bulk change of what
@@ -1404,6 +1428,7 @@ int flush(gsx_engine* e) {
     e->staged_inflight = true;
     const auto* dev = static_cast<const gsx::DevEvent*>(e->d_stage);
     const auto* doff = reinterpret_cast<const uint32_t*>(static_cast<const char*>(e->d_stage) + ev_bytes);
+    note_retained_events(e, e->pending);
     HIPCHK(e, gsx::launch_apply_events(dev_state(e), dev_peer_params(e), dev, doff, n_groups, e->stream));
     pending_clear(e);
     if (e->scores_valid || e->dirty_only || e->lazy) {  // exact but for these observers (and the stale pairs)
@@ -1868,6 +1893,9 @@ int load_overlay(gsx_engine* e, uint32_t n_total, uint32_t node_lo, uint32_t n_n
     e->n_tiles = (E + gsx::TILE - 1) / gsx::TILE;
     e->last_refresh = 0;
     e->phase = 0;
+    e->retained_possible = false;  // (the pair flags start all zero)
+    e->retain_horizon = INT64_MIN;
+    e->purge_launches = 0;
     e->row_ptr.assign(row_ptr, row_ptr + n_nodes + 1);
     e->col_host.assign(col, col + E);
     e->pair_obs.resize(E);
@@ -2385,7 +2413,17 @@ int gsx_refresh(gsx_engine* e, int64_t now) {
     int rc = flush(e);
     if (rc) return rc;
     const gsx::DevState s = dev_state(e);
-    HIPCHK(e, gsx::launch_purge(s, now, e->stream));
+    // The purge, only while a retained pair can exist (after the flush: its
+    // RemovePeers count).  One launched past the horizon has deleted every
+    // retained pair there was.
+    if (e->retained_possible) {
+        HIPCHK(e, gsx::launch_purge(s, now, e->stream));
+        ++e->purge_launches;
+        if (now > e->retain_horizon) {
+            e->retained_possible = false;
+            e->retain_horizon = INT64_MIN;
+        }
+    }
     const bool region = e->t_active && e->t_used < e->t_max;
     HIPCHK(e, hipEventRecord(region ? e->tev[2 * e->t_used] : e->ev_start, e->stream));
     HIPCHK(e, rescore_all(e, s, now, true));
@@ -2538,6 +2576,7 @@ int dropin_fast(gsx_engine* e) {
     if (!prs.empty()) std::memcpy(hb + pr_off, prs.data(), 8 * prs.size());
     std::atomic_thread_fence(std::memory_order_release);
     const uint32_t tag = ++e->dropin_tag;
+    note_retained_events(e, e->pending);
     HIPCHK(e, gsx::launch_dropin(dev_state(e), dev_peer_params(e), reinterpret_cast<const gsx::DevEvent*>(e->d_dropin + ev_off),
                                  reinterpret_cast<const uint32_t*>(e->d_dropin + go_off), (uint32_t)gobs.size(),
                                  reinterpret_cast<const uint32_t*>(e->d_dropin + ob_off), (uint32_t)rows.size(),
@@ -2690,7 +2729,16 @@ int gsx_import_state(gsx_engine* e, const gsx_state_view* s) {
     HIPCHK(e, hipMemsetAsync(e->d_nbad, 0, sizeof(uint32_t), e->stream));
     HIPCHK(e, hipMemcpyAsync(e->d_tmp, s->mesh_time_ns, 8 * R, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, gsx::launch_mesh_time_import(ds, static_cast<const int64_t*>(e->d_tmp), e->d_nbad, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->d_pflags, s->pair_flags, E, hipMemcpyHostToDevice, e->stream));
+    // The pair flags with epoch 0 (bp is current, the phase restarts), and the
+    // retained pairs among them: their largest expiry is the purge's horizon.
+    std::vector<uint8_t> pf(E);
+    e->retained_possible = false;
+    e->retain_horizon = INT64_MIN;
+    for (size_t p = 0; p < E; ++p) {
+        pf[p] = s->pair_flags[p] & (GSX_PAIR_PRESENT | GSX_PAIR_CONNECTED);
+        if (pf[p] == GSX_PAIR_PRESENT) note_retained(e, s->expire_ns[p]);
+    }
+    HIPCHK(e, hipMemcpyAsync(e->d_pflags, pf.data(), E, hipMemcpyHostToDevice, e->stream));  // (synchronised below)
     HIPCHK(e, hipMemcpyAsync(e->d_expire, s->expire_ns, 8 * E, hipMemcpyHostToDevice, e->stream));
     HIPCHK(e, hipMemcpyAsync(e->d_bp, s->behaviour_penalty, 8 * E, hipMemcpyHostToDevice, e->stream));
     if (int rc = pzmap_mark_p6(e)) return rc;  // new present bits, new counts
@@ -2728,6 +2776,16 @@ int gsx_synthesize_state(gsx_engine* e, const gsx_synth_spec* sp) {
     d.sybil_first = sp->sybil_first_node;
     e->last_refresh = sp->now_ns;  // meshTime = now - graftTime for every in-mesh record
     e->phase = 0;                  // (every record and flag byte is overwritten)
+    // k_synth_pairs makes retained pairs iff p_disc > 0, their expire within
+    // half the jitter of now (the draw is in [0, 1)); a jitter that is not
+    // exact as a double, or a sum that may not fit, leaves the bound unknown
+    e->retained_possible = false;
+    e->retain_horizon = INT64_MIN;
+    if (d.p_disc > 0) {
+        const int64_t j = d.expire_jitter, lim = 1ll << 53;
+        const bool fits = j > -lim && j < lim && d.now < (1ll << 62);
+        note_retained(e, fits ? d.now + (j < 0 ? -j : j) / 2 + 1 : kRetainUnknown);
+    }
     const gsx::DevState s = dev_state(e);
     HIPCHK(e, gsx::launch_synthesize(s, e->d_col, d, e->stream));
     if (int rc = pzmap_mark_p6(e)) return rc;  // new present bits, new counts
@@ -2762,9 +2820,16 @@ int gsx_export_state(gsx_engine* e, gsx_state_view* s) {
         HIPCHK(e, gsx::launch_untile_field(ds, gsx::NFIELD, e->d_tmp, e->stream));
         HIPCHK(e, hipMemcpyAsync(s->rec_flags, e->d_tmp, R, hipMemcpyDeviceToHost, e->stream));
     }
-    if (s->pair_flags) HIPCHK(e, hipMemcpyAsync(s->pair_flags, e->d_pflags, E, hipMemcpyDeviceToHost, e->stream));
+    // the pair flags without the epoch, bp with its pending decays (like the counters above)
+    if (s->pair_flags) {
+        HIPCHK(e, gsx::launch_pair_export(ds, static_cast<uint8_t*>(e->d_tmp), nullptr, e->stream));
+        HIPCHK(e, hipMemcpyAsync(s->pair_flags, e->d_tmp, E, hipMemcpyDeviceToHost, e->stream));
+    }
     if (s->expire_ns) HIPCHK(e, hipMemcpyAsync(s->expire_ns, e->d_expire, 8 * E, hipMemcpyDeviceToHost, e->stream));
-    if (s->behaviour_penalty) HIPCHK(e, hipMemcpyAsync(s->behaviour_penalty, e->d_bp, 8 * E, hipMemcpyDeviceToHost, e->stream));
+    if (s->behaviour_penalty) {
+        HIPCHK(e, gsx::launch_pair_export(ds, nullptr, static_cast<double*>(e->d_tmp), e->stream));
+        HIPCHK(e, hipMemcpyAsync(s->behaviour_penalty, e->d_tmp, 8 * E, hipMemcpyDeviceToHost, e->stream));
+    }
     HIPCHK(e, hipStreamSynchronize(e->stream));
     release_tmp(e);
     s->last_refresh_ns = e->last_refresh;
@@ -2820,6 +2885,13 @@ int gsx_pair_zero_map_violations(gsx_engine* e, uint64_t* n) { return pair_zero_
 int gsx_pair_zero_map_marked(gsx_engine* e, uint32_t which, uint64_t* n) {
     if (which != GSX_PZ_APP && which != GSX_PZ_P6) return GSX_EINVAL;
     return pair_zero_map_count(e, n, (int)which);
+}
+
+int gsx_purge_launches(gsx_engine* e, uint64_t* n) {
+    if (!e || !n) return GSX_EINVAL;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    *n = e->purge_launches;
+    return GSX_OK;
 }
 
 // inspectScoresExtended, score.go:463-493

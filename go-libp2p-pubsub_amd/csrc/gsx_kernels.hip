@@ -206,10 +206,23 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
             topic_step(t, tp, fmd, mmd, mfp, imd, graft, fl, zmt);
         }
     }
-    double bp = s.bp[p];
-    if (conn) {
-        bp = decay(bp, pp.d7, pp.decay_to_zero);
-        s.bp[p] = bp;
+    // The behaviour penalty under the same write-back (PAIR_EPOCH): its pending
+    // decays and this refresh's in registers, the count scalar when the wave
+    // agrees on it; stored, if it changed, only by the refresh that completes
+    // a period, which also brings the pair's epoch to the new phase, 0.  The
+    // flag byte is not written otherwise.
+    const double bp0 = s.bp[p];
+    double bp = bp0;
+    const uint32_t nb = (lag ? (phase - ((uint32_t)st >> PAIR_EPOCH_SHIFT)) & 3u : 0u) + (conn ? 1u : 0u);
+    const uint32_t nb0 = __builtin_amdgcn_readfirstlane(nb);
+    if (__ballot(nb != nb0) == 0) {
+        for (uint32_t i = 0; i < nb0; ++i) bp = decay(bp, pp.d7, pp.decay_to_zero);
+    } else {
+        for (uint32_t i = 0; i < nb; ++i) bp = decay(bp, pp.d7, pp.decay_to_zero);
+    }
+    if (wb && conn) {
+        if (__double_as_longlong(bp) != __double_as_longlong(bp0)) s.bp[p] = bp;
+        if (st & PAIR_EPOCH) s.pflags[p] = st & ~PAIR_EPOCH;
     }
     // score_tail (gsx_ops.h) behind the pair zero map.  Both tests are the
     // wave's (pz is scalar): a tile whose entry says zero gathers nothing.
@@ -636,9 +649,36 @@ __global__ __launch_bounds__(256) void k_materialize(DevState s) {
     if (k) rec_store_decayed(s, p, t, k);
     if (fl & REC_EPOCH) s.rflags[fi] = fl & ~REC_EPOCH;
 }
+// The same for every pair's behaviour penalty and epoch (PAIR_EPOCH); after
+// k_materialize, which reads the pair flags' connected bit.
+__global__ __launch_bounds__(256) void k_materialize_pairs(DevState s) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (p >= s.n_pairs) return;
+    const uint8_t st = s.pflags[p];
+    const uint32_t k = bp_pend(s, st);
+    if (k) {
+        const double o = s.bp[p], v = bp_decay(o, s.d7, s.decay_to_zero, k);
+        if (__double_as_longlong(v) != __double_as_longlong(o)) s.bp[p] = v;
+    }
+    if (st & PAIR_EPOCH) s.pflags[p] = st & ~PAIR_EPOCH;
+}
 hipError_t launch_materialize(const DevState& s, hipStream_t st) {
     if (s.n_pairs == 0) return hipSuccess;
     hipLaunchKernelGGL(k_materialize, dim3(blocks_for(s.n_pairs, 256), s.n_topics), dim3(256), 0, st, s);
+    hipLaunchKernelGGL(k_materialize_pairs, dim3(blocks_for(s.n_pairs, 256)), dim3(256), 0, st, s);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void k_pair_export(DevState s, uint8_t* __restrict__ pf, double* __restrict__ bp) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (p >= s.n_pairs) return;
+    const uint8_t st = s.pflags[p];
+    if (pf) pf[p] = st & ~PAIR_EPOCH;
+    if (bp) bp[p] = bp_read(s, p, st);
+}
+hipError_t launch_pair_export(const DevState& s, uint8_t* pflags, double* bp, hipStream_t st) {
+    if (s.n_pairs == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_pair_export, dim3(blocks_for(s.n_pairs, 256)), dim3(256), 0, st, s, pflags, bp);
     return hipGetLastError();
 }
 

@@ -230,6 +230,37 @@ __device__ __forceinline__ uint8_t rec_materialize(const DevState& s, uint64_t p
     return rec_materialize(s, p, t, s.pflags[p]);
 }
 
+// ---- the behaviour penalty under the same write-back (PAIR_EPOCH, gsx_device.h) ----
+// decays of d7 the stored bp of a pair with flags st lags by
+__device__ __forceinline__ uint32_t bp_pend(const DevState& s, uint8_t st) {
+    return (st & PAIR_CONNECTED) ? ((s.phase - ((uint32_t)st >> PAIR_EPOCH_SHIFT)) & 3u) : 0u;
+}
+
+__device__ __forceinline__ double bp_decay(double bp, double d7, double dtz, uint32_t k) {
+    for (uint32_t i = 0; i < k; ++i) bp = decay(bp, d7, dtz);
+    return bp;
+}
+
+// The pair's behaviour penalty as of the last refresh; stores nothing.
+__device__ __forceinline__ double bp_read(const DevState& s, uint64_t p, uint8_t st) {
+    return bp_decay(s.bp[p], s.d7, s.decay_to_zero, bp_pend(s, st));
+}
+
+// Brings the stored bp of a connected pair up to date and its epoch to the
+// current phase (before any read-modify-write of bp, and before the pair stops
+// being decayed).  -> the flag byte as stored.
+__device__ __forceinline__ uint8_t bp_materialize(const DevState& s, uint64_t p, uint8_t st) {
+    if (!(st & PAIR_CONNECTED)) return st;
+    const uint32_t k = bp_pend(s, st);
+    if (k) {
+        const double o = s.bp[p], v = bp_decay(o, s.d7, s.decay_to_zero, k);
+        if (__double_as_longlong(v) != __double_as_longlong(o)) s.bp[p] = v;
+    }
+    const uint8_t nf = (uint8_t)((st & ~PAIR_EPOCH) | ((s.phase & 3u) << PAIR_EPOCH_SHIFT));
+    if (nf != st) s.pflags[p] = nf;
+    return nf;
+}
+
 // score(p) from the stored state, no refresh (RemovePeer, score.go:615).
 __device__ __forceinline__ double eval_pair(const DevState& s, const DevPeerParams& pp, uint64_t p) {
     const uint8_t st = s.pflags[p];
@@ -242,7 +273,7 @@ __device__ __forceinline__ double eval_pair(const DevState& s, const DevPeerPara
         const RecVals v = rec_read(s, p, t, st, fl);
         score += topic_score(tp, fl, mesh_time_of(s, fl, p, t), v.fmd, v.mmd, v.mfp, v.imd);
     }
-    return score_tail(s, pp, p, score, s.bp[p]);
+    return score_tail(s, pp, p, score, bp_read(s, p, st));
 }
 
 // k steps of "x = x + 1; if x > cap { x = cap }" (score.go:925-938, 970-973),
@@ -326,7 +357,10 @@ __device__ inline void ev_add_peer(const DevState& s, const DevPeerParams& pp, u
             if ((fl & REC_EPOCH) != ep) s.rflags[fi] = (uint8_t)((fl & ~REC_EPOCH) | ep);
         }
     }
-    s.pflags[p] = PAIR_PRESENT | PAIR_CONNECTED;
+    // a new or reconnecting pair's bp is current as of this phase; a connected
+    // pair keeps its epoch
+    if (!(st & PAIR_PRESENT) || !(st & PAIR_CONNECTED))
+        s.pflags[p] = (uint8_t)(PAIR_PRESENT | PAIR_CONNECTED | ((s.phase & 3u) << PAIR_EPOCH_SHIFT));
 }
 
 __device__ inline void ev_remove_peer(const DevState& s, const DevPeerParams& pp, uint64_t p, int64_t now) {  // :604-637
@@ -334,6 +368,7 @@ __device__ inline void ev_remove_peer(const DevState& s, const DevPeerParams& pp
     if (!(st & PAIR_PRESENT)) return;
     if (eval_pair(s, pp, p) > 0) {  // positive score: forget the peer
         ipcount_add(s, p, -1);
+        bp_materialize(s, p, st);  // (an absent pair's bp is exported as stored)
         s.pflags[p] = 0;
         return;
     }
@@ -355,6 +390,7 @@ __device__ inline void ev_remove_peer(const DevState& s, const DevPeerParams& pp
         }
         s.rflags[fi] = fl & ~(REC_IN_MESH | REC_FRESH);
     }
+    bp_materialize(s, p, st);  // (and bp, before the pair stops being decayed)
     s.pflags[p] = PAIR_PRESENT;
     s.expire[p] = now + pp.retain_ns;
 }
@@ -414,7 +450,9 @@ __device__ inline void ev_invalid(const DevState& s, uint64_t p, uint32_t topic)
 }
 
 __device__ inline void ev_penalty(const DevState& s, uint64_t p, int64_t count) {  // AddPenalty :384-398
-    if (!(s.pflags[p] & PAIR_PRESENT)) return;
+    const uint8_t st = s.pflags[p];
+    if (!(st & PAIR_PRESENT)) return;
+    bp_materialize(s, p, st);
     s.bp[p] = s.bp[p] + (double)count;
 }
 

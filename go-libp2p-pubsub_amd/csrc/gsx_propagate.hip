@@ -1838,7 +1838,7 @@ __device__ __forceinline__ double eval_pair_cached(const PropState& ps, const De
         }
         ps.tgen[q] = ps.tepoch;
     }
-    return score_tail(s, pp, q, score, s.bp[q]);
+    return score_tail(s, pp, q, score, bp_read(s, q, s.pflags[q]));
 }
 
 // k_prop_count's fold + re-score for one topic (the propagation engines'
@@ -1918,7 +1918,7 @@ __device__ __forceinline__ void fold_rescore_1(const PropState& ps, const DevSta
         imd[j] = s.rec[b + IMD * TILE];
         graft[j] = reinterpret_cast<const int64_t*>(s.rec)[rec_index(q, t, 1, GRAFT)];
         app[j] = s.app[q];
-        bp[j] = s.bp[q];
+        bp[j] = bp_read(s, q, s.pflags[q]);
         if (pp.w6 != 0.0) ipg[j] = reinterpret_cast<const uint2*>(s.ipg)[q];
     }
     uint32_t ipc[FH][2];

@@ -1289,3 +1289,9 @@ class Engine:
         n = C.c_uint64()
         self._chk(self.lib.gsx_pair_zero_map_marked(self.h, which, C.byref(n)), "gsx_pair_zero_map_marked")
         return n.value
+
+    def purge_launches(self) -> int:
+        """gsx_purge_launches: launches of the purge of expired retained peers since the overlay was loaded."""
+        n = C.c_uint64()
+        self._chk(self.lib.gsx_purge_launches(self.h, C.byref(n)), "gsx_purge_launches")
+        return n.value

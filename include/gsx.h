@@ -422,8 +422,19 @@ int gsx_pair_zero_map_marked(gsx_engine* e, uint32_t which, uint64_t* n);
  * which every reader applies on the fly and every writer (events, credits,
  * heartbeats) settles for its record first, so no result changes: scores,
  * gsx_export_state and every other output are bit-identical for every k.
- * k = 1 stores at every refresh.  Settles every record before switching. */
+ * k = 1 stores at every refresh.  Settles every record before switching.
+ * A pair's behaviour penalty follows the same period: between stores it lags
+ * by the same decays of BehaviourPenaltyDecay, counted in two bits of the
+ * device's pair flag byte; gsx_export_state applies them as it does the
+ * counters', so its pair_flags hold only GSX_PAIR_PRESENT | GSX_PAIR_CONNECTED
+ * and its behaviour_penalty the current values. */
 int gsx_set_decay_writeback(gsx_engine* e, uint32_t k);
+/* *n = the launches of the purge of expired retained peers (refreshScores,
+ * score.go:503-515) since the overlay was loaded.  gsx_refresh launches it
+ * only while a pair that is present and not connected can exist: after a
+ * RemovePeer, an imported state that holds one, or a synthesized state with
+ * p_disconnected > 0, until a refresh later than every such pair's expiry. */
+int gsx_purge_launches(gsx_engine* e, uint64_t* n);
 
 /* WithPeerScoreInspect's extended view (ExtendedPeerScoreInspectFn,
  * inspectScoresExtended score.go:463-493): a PeerScoreSnapshot per pair
