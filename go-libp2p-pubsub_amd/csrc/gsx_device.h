@@ -422,6 +422,26 @@ hipError_t launch_prop_hops_export(const PropState& ps, uint8_t* hop_mn, hipStre
 constexpr uint32_t PROP_STATS_HOPS = 65;  // GSX_MAX_HOPS + 1
 hipError_t launch_prop_stats(const PropState& ps, uint32_t* msg_hop_hist, uint32_t* node_received,
                              unsigned long long* node_hop_sum, hipStream_t st);
+// gsx_prop_traffic (gsx_prop_traffic.hip): the copies of the last call (one
+// per message k sent by v to u) by what u's router did with them, and their
+// bytes.  sset is scratch ([node][n_words]: what each node sent at a hop that
+// ran); planes [n_planes][n_words] are the bit planes of the message sizes
+// (bit b of planes[j][w]: bit j of the size of message 64 w + b; null: every
+// message counts 1 byte).  Any output may be null; the launcher overwrites
+// the others (it zeroes what its kernels add to).
+constexpr uint32_t TRAFFIC_COLS = 5;  // GSX_TRAFFIC_COLS
+enum { TR_SENT = 0, TR_FIRST = 1, TR_DUP = 2, TR_INVALID = 3, TR_GRAY = 4 };  // GSX_TRAFFIC_*
+struct TrafficArgs {
+    uint64_t* sset;
+    const uint64_t* planes;
+    uint32_t n_planes;
+    uint32_t* msg_copies;            // [n_msgs][TRAFFIC_COLS]
+    uint32_t* node_copies;           // [n_nodes][TRAFFIC_COLS]
+    unsigned long long* node_bytes;  // [n_nodes][2]: sent, received
+    uint32_t* pair_copies;           // [n_pairs]
+    unsigned long long* pair_bytes;  // [n_pairs]
+};
+hipError_t launch_prop_traffic(const PropState& ps, const TrafficArgs& a, hipStream_t st);
 // gsx_propagate_timed (gsx_prop_timed.hip): propagation on a tick clock with a
 // latency per directed link.  The call's setup (fwd / pin / compacted senders)
 // is the PropState's, built by launch_prop_fwd; everything else is here.

@@ -429,6 +429,15 @@ struct gsx_engine {
         size_t st_hist_cap = 0;
         uint32_t* st_recv = nullptr;
         unsigned long long* st_sum = nullptr;
+        // gsx_prop_traffic: its scratch rows ([node][word]), the size planes, and the
+        // device side of outputs that go to host memory, each grown on demand
+        uint64_t *tr_sset = nullptr, *tr_planes = nullptr;
+        uint32_t *tr_msg = nullptr, *tr_node = nullptr, *tr_pair = nullptr;
+        unsigned long long *tr_nbytes = nullptr, *tr_pbytes = nullptr;
+        size_t tr_sset_cap = 0, tr_planes_cap = 0, tr_msg_cap = 0, tr_node_cap = 0, tr_pair_cap = 0, tr_nbytes_cap = 0,
+               tr_pbytes_cap = 0;
+        std::vector<uint64_t> tr_hplanes;  // (host staging of the planes, alive until their upload is done)
+        bool tr_planes_busy = false;
         // gsx_score_stats: the same for its five outputs, each sized once for
         // GSX_SS_MAX_EDGES + 1 bins (per node, never per pair)
         unsigned long long* ss_hist = nullptr;
@@ -1085,6 +1094,8 @@ void free_state(gsx_engine* e) {
                   e->prop.src_bits, e->prop.src_ids, e->prop.src_rows,
                   e->prop.d_dig, e->prop.rcand, e->prop.tterm, e->prop.tgen, e->prop.hist_alt, e->prop.occ_alt,
                   e->prop.st_hist, e->prop.st_recv, e->prop.st_sum,
+                  e->prop.tr_sset, e->prop.tr_planes, e->prop.tr_msg, e->prop.tr_node, e->prop.tr_pair,
+                  e->prop.tr_nbytes, e->prop.tr_pbytes,
                   e->prop.ss_hist, e->prop.ss_obs_bins, e->prop.ss_peer_bins, e->prop.ss_obs_min, e->prop.ss_peer_min};
     for (void* p : pp)
         if (p) (void)hipFree(p);
@@ -4282,6 +4293,118 @@ int gsx_prop_stats(gsx_engine* e, uint32_t* msg_hop_hist, uint32_t* node_receive
         host = true;
     }
     if (host) HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GSX_OK;
+}
+
+// One output of gsx_prop_traffic by gsx_prop_stats' pointer rules: device
+// memory is written in place, host memory gets a copy of an engine buffer
+// (grown on demand), NULL is skipped.
+extern "C++" {
+template <typename T>
+static int traffic_grow(gsx_engine* e, T** buf, size_t* cap, size_t n) {
+    if (*cap >= n) return GSX_OK;
+    if (*buf) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        (void)hipFree(*buf);
+    }
+    *buf = nullptr;
+    *cap = 0;
+    if (int rc = dalloc(e, buf, n)) return rc;
+    *cap = n;
+    return GSX_OK;
+}
+template <typename T>
+static int traffic_out(gsx_engine* e, T* user, T** buf, size_t* cap, size_t n, T** dev) {
+    *dev = nullptr;
+    if (!user) return GSX_OK;
+    if (on_device(user)) {
+        *dev = user;
+        return GSX_OK;
+    }
+    if (int rc = traffic_grow(e, buf, cap, n)) return rc;
+    *dev = *buf;
+    return GSX_OK;
+}
+}  // extern "C++"
+
+int gsx_prop_traffic(gsx_engine* e, const uint32_t* msg_bytes, uint32_t* msg_copies, uint32_t* node_copies,
+                     uint64_t* node_bytes, uint32_t* pair_copies, uint64_t* pair_bytes) {
+    static_assert(gsx::TRAFFIC_COLS == GSX_TRAFFIC_COLS && gsx::TR_SENT == GSX_TRAFFIC_SENT &&
+                      gsx::TR_FIRST == GSX_TRAFFIC_FIRST && gsx::TR_DUP == GSX_TRAFFIC_DUP &&
+                      gsx::TR_INVALID == GSX_TRAFFIC_INVALID && gsx::TR_GRAY == GSX_TRAFFIC_GRAYLISTED,
+                  "the kernels' columns are the header's");
+    if (!e) return GSX_EINVAL;
+    auto& P = e->prop;
+    if (e->sharded()) return fail(e, GSX_EINVAL, "traffic is counted by unsharded engines only");
+    if (!P.have_last) return fail(e, GSX_ESTATE, "no propagation call yet");
+    if (e->tprop.after) return fail(e, GSX_ESTATE, "the last propagation was a timed call (its copies have arrival ticks, not hops)");
+    if (P.active) return fail(e, GSX_ESTATE, "a stepped propagation is in flight");
+    gsx::PropState ps = P.last;
+    ps.n_rows = P.rows_valid;
+    const size_t m = ps.n_msgs, N = ps.n_nodes, E = e->E, W = ps.n_words;
+    // a node's counter takes at most one copy per (pair of its row, message) and per (pair it is the neighbour of, message)
+    if ((uint64_t)e->max_deg * m >= (1ull << 32))
+        return fail(e, GSX_EINVAL, "longest row x messages >= 2^32: a u32 node counter could wrap");
+    if (!ps.from_mask)
+        return fail(e, GSX_ESTATE, "first deliverers were not tracked in the last call (gsx_prop_set_tracking)");
+    if (m == 0 || E == 0 || N == 0) return GSX_OK;
+    if (!msg_copies && !node_copies && !node_bytes && !pair_copies && !pair_bytes) return GSX_OK;
+    gsx::TrafficArgs a{};
+    unsigned long long *d_nb = nullptr, *d_pb = nullptr;
+    if (int rc = traffic_out(e, msg_copies, &P.tr_msg, &P.tr_msg_cap, m * gsx::TRAFFIC_COLS, &a.msg_copies)) return rc;
+    if (int rc = traffic_out(e, node_copies, &P.tr_node, &P.tr_node_cap, N * gsx::TRAFFIC_COLS, &a.node_copies)) return rc;
+    if (int rc = traffic_out(e, reinterpret_cast<unsigned long long*>(node_bytes), &P.tr_nbytes, &P.tr_nbytes_cap, 2 * N, &d_nb))
+        return rc;
+    if (int rc = traffic_out(e, pair_copies, &P.tr_pair, &P.tr_pair_cap, E, &a.pair_copies)) return rc;
+    if (int rc = traffic_out(e, reinterpret_cast<unsigned long long*>(pair_bytes), &P.tr_pbytes, &P.tr_pbytes_cap, E, &d_pb))
+        return rc;
+    a.node_bytes = d_nb;
+    a.pair_bytes = d_pb;
+    // the scratch rows, kept with the engine (dropped with the overlay)
+    if (int rc = traffic_grow(e, &P.tr_sset, &P.tr_sset_cap, N * W)) return rc;
+    a.sset = P.tr_sset;
+    if (msg_bytes && (a.node_bytes || a.pair_bytes)) {
+        // bit planes of the sizes, only up to the highest bit used: [plane][word] (at least one word, so
+        // that sizes of all 0 are not taken for "no sizes")
+        if (P.tr_planes_busy) HIPCHK(e, hipStreamSynchronize(e->stream));  // (the last upload may still read them)
+        P.tr_planes_busy = false;
+        uint32_t any = 0;
+        for (size_t k = 0; k < m; ++k) any |= msg_bytes[k];
+        uint32_t np = 0;
+        while (np < 32 && (any >> np)) ++np;
+        P.tr_hplanes.assign(std::max<size_t>((size_t)np * W, 1), 0);
+        for (size_t k = 0; k < m; ++k)
+            for (uint32_t b = msg_bytes[k], j = 0; b; b >>= 1, ++j)
+                if (b & 1) P.tr_hplanes[(size_t)j * W + k / 64] |= 1ull << (k % 64);
+        if (int rc = traffic_grow(e, &P.tr_planes, &P.tr_planes_cap, P.tr_hplanes.size())) return rc;
+        HIPCHK(e, hipMemcpyAsync(P.tr_planes, P.tr_hplanes.data(), 8 * P.tr_hplanes.size(), hipMemcpyHostToDevice,
+                                 e->stream));
+        P.tr_planes_busy = true;
+        a.planes = P.tr_planes;
+        a.n_planes = np;
+    }
+    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
+    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    HIPCHK(e, gsx::launch_prop_traffic(ps, a, e->stream));
+    if (region) {
+        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
+        ++e->t_used;
+    }
+    bool host = false;
+    auto back = [&](void* user, const void* dev, size_t bytes) -> hipError_t {
+        if (!user || user == dev) return hipSuccess;
+        host = true;
+        return hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, e->stream);
+    };
+    HIPCHK(e, back(msg_copies, a.msg_copies, 4 * m * gsx::TRAFFIC_COLS));
+    HIPCHK(e, back(node_copies, a.node_copies, 4 * N * gsx::TRAFFIC_COLS));
+    HIPCHK(e, back(node_bytes, a.node_bytes, 8 * 2 * N));
+    HIPCHK(e, back(pair_copies, a.pair_copies, 4 * E));
+    HIPCHK(e, back(pair_bytes, a.pair_bytes, 8 * E));
+    if (host) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        P.tr_planes_busy = false;
+    }
     return GSX_OK;
 }
 

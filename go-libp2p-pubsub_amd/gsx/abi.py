@@ -227,6 +227,9 @@ GSX_ROUTER_FLOODSUB = 0
 GSX_ROUTER_GOSSIPSUB = 1
 GSX_ROUTER_RANDOMSUB = 2
 GSX_MAX_HOPS = 64
+# gsx_prop_traffic's columns
+GSX_TRAFFIC_SENT, GSX_TRAFFIC_FIRST, GSX_TRAFFIC_DUP, GSX_TRAFFIC_INVALID, GSX_TRAFFIC_GRAYLISTED = range(5)
+GSX_TRAFFIC_COLS = 5
 GXF_MAX_HOPS = 4096  # hops of one forwarding run of the gossip exchange (gsx_device.h)
 GSX_CREDIT_OFF = 0
 GSX_CREDIT_NOW = 1
@@ -608,6 +611,9 @@ SIGNATURES = {
     "gsx_score_stats": (C.c_int, [C.c_void_p, P(ScoreStatsSpec), P(ScoreStatsOut)]),
     "gsx_prop_set_tracking": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_prop_duplicates": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_size_t]),
+    # (msg_bytes: host; the outputs host or device pointers, like gsx_prop_stats: passed as addresses)
+    "gsx_prop_traffic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "gsx_set_pair_ips": (C.c_int, [C.c_void_p, P(C.c_uint64), P(C.c_uint32), C.c_size_t]),
     "gsx_peer_score_snapshot": (C.c_int, [C.c_void_p, P(ScoreSnapshot)]),
     "gsx_prop_pending_invalid": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -118,6 +118,87 @@ class PropStats:
                          sum(p.node_hop_sum for p in parts) if per_node else None)
 
 
+class PropTraffic:
+    """What a propagation call cost (gsx_prop_traffic).  A copy is message k sent by v to u;
+    the columns are SENT (every copy) and the four classes FIRST, DUP, INVALID, GRAYLISTED by
+    what u's router did with it.  msg[k, c]: copies of message k; node[u, SENT]: copies u sent,
+    node[u, c] otherwise: copies of class c that reached u; node_bytes[u] = (bytes u sent, bytes
+    that reached u); pair[q] / pair_bytes[q]: the copies pair q's neighbour sent its observer.
+    Any table may be None (not asked for).  Numpy on those integers; nothing here touches the
+    device."""
+
+    SENT, FIRST, DUP, INVALID, GRAYLISTED = range(abi.GSX_TRAFFIC_COLS)
+    COLS = abi.GSX_TRAFFIC_COLS
+
+    def __init__(self, msg=None, node=None, node_bytes=None, pair=None, pair_bytes=None):
+        def arr(x, dt, shape):
+            return None if x is None else np.ascontiguousarray(x, dtype=dt).reshape(shape)
+
+        self.msg = arr(msg, np.uint32, (-1, self.COLS))
+        self.node = arr(node, np.uint32, (-1, self.COLS))
+        self.node_bytes = arr(node_bytes, np.uint64, (-1, 2))
+        self.pair = arr(pair, np.uint32, (-1,))
+        self.pair_bytes = arr(pair_bytes, np.uint64, (-1,))
+
+    def total(self, col: int) -> int:
+        """Copies of a column over the whole call (from the per-message table, else the per-node one)."""
+        t = self.msg if self.msg is not None else self.node
+        return int(t[:, col].astype(np.int64).sum())
+
+    def sent(self) -> int:
+        """Every copy of the call: gsx_prop_out.transmissions."""
+        return self.total(self.SENT)
+
+    def amplification(self) -> np.ndarray:
+        """[m] f64: copies sent per first receipt of the message, SENT / max(FIRST + INVALID, 1)."""
+        t = self.msg.astype(np.int64)
+        return t[:, self.SENT] / np.maximum(t[:, self.FIRST] + t[:, self.INVALID], 1)
+
+    def duplicate_ratio(self) -> np.ndarray:
+        """[n] f64: the share of the copies that reached a node which it had already seen (0 where none did)."""
+        t = self.node.astype(np.int64)
+        got = t[:, self.FIRST:].sum(1)
+        return np.where(got > 0, t[:, self.DUP] / np.maximum(got, 1), 0.0)
+
+    def upload_bytes(self) -> np.ndarray:
+        return self.node_bytes[:, 0]
+
+    def download_bytes(self) -> np.ndarray:
+        return self.node_bytes[:, 1]
+
+    def busiest(self, k: int, by: str = "upload_bytes") -> np.ndarray:
+        """The k node ids with the largest `by` ("upload_bytes", "download_bytes", "sent" or
+        "received" copies), largest first, ties broken by ascending id."""
+        if by in ("upload_bytes", "download_bytes"):
+            key = getattr(self, by)()
+        elif by == "sent":
+            key = self.node[:, self.SENT]
+        elif by == "received":
+            key = self.node[:, self.FIRST:].astype(np.int64).sum(1)
+        else:
+            raise ValueError(f"busiest by {by!r}")
+        # ascending by (key, -id), reversed: key descending, equal keys by ascending id
+        order = np.lexsort((-np.arange(len(key), dtype=np.int64), key))[::-1]
+        return order[: max(int(k), 0)].astype(np.int64)
+
+    @staticmethod
+    def concat(parts) -> "PropTraffic":
+        """Message-parallel replicas, in rank order: the message rows follow one another, the node and
+        pair tables (kept when every part has them) add up."""
+        parts = list(parts)
+
+        def add(name, dt):
+            xs = [getattr(p, name) for p in parts]
+            if not xs or any(x is None for x in xs):
+                return None
+            return sum(x.astype(np.uint64) for x in xs).astype(dt)
+
+        msgs = [p.msg for p in parts]
+        msg = None if not msgs or any(x is None for x in msgs) else np.concatenate(msgs, 0)
+        return PropTraffic(msg, add("node", np.uint32), add("node_bytes", np.uint64), add("pair", np.uint32),
+                           add("pair_bytes", np.uint64))
+
+
 class TimedStats:
     """Per-message arrival-time summary of a timed propagation (gsx_timed_stats):
     tick_hist[k, b] = nodes whose arrival tick a of message k has min(a // bin_ticks,
@@ -441,6 +522,7 @@ class Engine:
             self.lib.gsx_propagate(self.h, ms.ctypes.data_as(C.c_void_p), len(ms), C.byref(cfg), C.byref(out)),
             "gsx_propagate",
         )
+        self._traffic_m = len(ms)
         hop = frm = None
         if want_results:
             n = self.n_nodes
@@ -747,6 +829,7 @@ class Engine:
         self._chk(self.lib.gsx_prop_begin(self.h, ms.ctypes.data_as(C.c_void_p), len(ms), C.byref(cfg)),
                   "gsx_prop_begin")
         self._prop_msgs = len(ms)
+        self._traffic_m = len(ms)
 
     def prop_pack(self, send):
         """send: device buffer (torch tensor or pointer) of [n_send][words] u64 rows."""
@@ -846,6 +929,43 @@ class Engine:
                                           C.c_void_p(hsum.ctypes.data if per_node and hsum.size else None)),
                   "gsx_prop_stats")
         return PropStats(hist, recv, hsum)
+
+    def prop_traffic(self, n_msgs: int, msg_bytes=None, per_node: bool = True, per_pair: bool = False, out_ptrs=None):
+        """gsx_prop_traffic of the last propagation (n_msgs: its messages) -> PropTraffic: msg
+        [m, 5] u32 and, with per_node, node [n, 5] u32 and node_bytes [n, 2] u64, with per_pair,
+        pair [n_pairs] u32 and pair_bytes [n_pairs] u64.  msg_bytes: [m] u32 sizes (None: 1 byte
+        each, so bytes == copies).  n_msgs must be the last call's message count, as for
+        prop_stats: the library reads and writes that many entries; after a propagate() or
+        prop_begin() through this handle a different n_msgs raises ValueError.
+
+        out_ptrs = (msg, node, node_bytes, pair, pair_bytes): device pointers or tensors (None /
+        0 skips one) written in stream order with no host sync, as prop_stats takes them; then
+        -> None."""
+        last = getattr(self, "_traffic_m", None)
+        if last is not None and int(n_msgs) != last:
+            raise ValueError(f"n_msgs is {n_msgs}, the last propagation had {last} messages")
+        sizes = None
+        if msg_bytes is not None:
+            sizes = np.ascontiguousarray(msg_bytes, dtype=np.uint32)
+            if sizes.shape != (n_msgs,):
+                raise ValueError("msg_bytes holds one size per message of the call")
+        sp = C.c_void_p(sizes.ctypes.data if sizes is not None and sizes.size else None)
+        if sizes is not None and not sizes.size:
+            sizes = None
+        if out_ptrs is not None:
+            self._chk(self.lib.gsx_prop_traffic(self.h, sp, *[self._p(p) if p is not None else None for p in out_ptrs]),
+                      "gsx_prop_traffic")
+            return None
+        n, E, K = self.n_nodes, self.n_pairs, abi.GSX_TRAFFIC_COLS
+        msg = np.zeros((n_msgs, K), dtype=np.uint32)
+        node = np.zeros((n, K), dtype=np.uint32) if per_node else None
+        nbytes = np.zeros((n, 2), dtype=np.uint64) if per_node else None
+        pair = np.zeros(E, dtype=np.uint32) if per_pair else None
+        pbytes = np.zeros(E, dtype=np.uint64) if per_pair else None
+        self._chk(self.lib.gsx_prop_traffic(self.h, sp, *[C.c_void_p(a.ctypes.data if a is not None and a.size else None)
+                                                          for a in (msg, node, nbytes, pair, pbytes)]),
+                  "gsx_prop_traffic")
+        return PropTraffic(msg, node, nbytes, pair, pbytes)
 
     def score_stats_edges(self) -> np.ndarray:
         """gsx_score_stats_edges: the sorted, de-duplicated thresholds of the last set_thresholds and 0.0."""

@@ -722,6 +722,39 @@ class MessageParallel:
             nd = nd.cpu().numpy()
             return PropStats(table, nd[0], nd[1].view(np.uint64))
 
+    def prop_traffic(self, n_msgs: int, msg_bytes=None, per_node: bool = True, per_pair: bool = False):
+        """gsx_prop_traffic of the last propagate() of n_msgs messages -> PropTraffic of the whole
+        batch, laid out like prop_stats: every replica counts its bounds(n_msgs) slice (with that
+        slice of msg_bytes); the message rows are all-gathered (padded to the largest slice) and
+        concatenated, the node and pair tables summed over the replicas.  Raises the engine's
+        error when the replicas ran without first-deliverer tracking."""
+        torch = _torch()
+        from .engine import PropTraffic
+
+        with self._on_stream():
+            dev, w, K = self.tp.device, self.tp.world, abi.GSX_TRAFFIC_COLS
+            counts = [(n_msgs * (k + 1)) // w - (n_msgs * k) // w for k in range(w)]
+            lo, hi = self.bounds(n_msgs)
+            sizes = None if msg_bytes is None else np.ascontiguousarray(msg_bytes, dtype=np.uint32)[lo:hi]
+            m32 = torch.zeros((max(counts + [0]), K), dtype=torch.int32, device=dev)
+            n, E = self.e.n_nodes, self.e.n_pairs
+            node = torch.zeros((n, K), dtype=torch.int32, device=dev) if per_node else None
+            nbytes = torch.zeros((n, 2), dtype=torch.int64, device=dev) if per_node else None
+            pair = torch.zeros(E, dtype=torch.int32, device=dev) if per_pair else None
+            pbytes = torch.zeros(E, dtype=torch.int64, device=dev) if per_pair else None
+            if counts[self.tp.rank]:
+                self.e.prop_traffic(counts[self.tp.rank], sizes, out_ptrs=(m32, node, nbytes, pair, pbytes))
+            parts = self.tp.all_gather(m32)
+            table = torch.cat([parts[k][: counts[k]] for k in range(w)], 0).cpu().numpy().view(np.uint32)
+            out = [table, None, None, None, None]
+            for i, t in ((1, node), (2, nbytes), (3, pair), (4, pbytes)):
+                if t is None:
+                    continue
+                s = t.to(torch.int64) & 0xFFFFFFFF if t.dtype == torch.int32 else t.clone()
+                self.tp.all_reduce_sum(s)
+                out[i] = s.cpu().numpy().view(np.uint64) if t.dtype == torch.int64 else s.cpu().numpy()
+            return PropTraffic(*out)
+
     def _merge_cache(self, msgs, cfg, n_mine: int):
         """One all-gather of the replicas' cache blocks; every replica Puts the whole batch."""
         m, w = len(msgs), self.tp.world

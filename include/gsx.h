@@ -627,6 +627,52 @@ int gsx_prop_stats(gsx_engine* e, uint32_t* msg_hop_hist, uint32_t* node_receive
  * reference's per-copy tracer call with one export (f4).  Host buffer of
  * n_pairs * n_words u64. */
 int gsx_prop_duplicates(gsx_engine* e, uint64_t* rows, size_t n_words);
+/* What the last propagation cost: its copies per message, per node and per
+ * link, and their bytes, reduced on the device.  One copy is message k sent
+ * by v to u: one unit of gsx_prop_out.transmissions.  Every copy belongs to
+ * exactly one of the classes FIRST .. GRAYLISTED, by what u's router did with
+ * it; the column SENT counts every copy:
+ *   GSX_TRAFFIC_SENT        every copy, whatever became of it
+ *   GSX_TRAFFIC_FIRST       u's first receipt of an ACCEPT message (a delivery)
+ *   GSX_TRAFFIC_DUP         u had already seen k (gsx_prop_duplicates' bits)
+ *   GSX_TRAFFIC_INVALID     u's first receipt of a REJECT / IGNORE / THROTTLE message
+ *   GSX_TRAFFIC_GRAYLISTED  dropped by u's AcceptFrom before pushMsg (score below
+ *                           graylist, or AcceptControl under gsx_gater_enforce)
+ * so the column sums are gsx_prop_out's transmissions, deliveries, duplicates,
+ * rejected + ignored and graylisted.  v sends what it forwarded at a hop that
+ * ran (its own messages at hop 0), through the eligibility of its pair
+ * (v -> u) or RandomSub's draw, never to the peer it first got k from nor to
+ * k's origin.  "The copies of pair q = (u -> v)" are those v sent to u.
+ *   msg_copies[k * GSX_TRAFFIC_COLS + c]   copies of message k in column c
+ *   node_copies[u * GSX_TRAFFIC_COLS + c]  c = SENT: copies u sent; else: copies
+ *                                          of class c that reached u
+ *   node_bytes[2 u], [2 u + 1]             bytes u sent; bytes that reached u (all
+ *                                          four classes)
+ *   pair_copies[q], pair_bytes[q]          the copies of q (all classes), their bytes
+ * msg_bytes is host memory: the sizes of the last call's n_msgs messages (any
+ * u32, 0 included); NULL counts every message as 1 byte, so bytes == copies.
+ * The output pointers follow gsx_prop_stats' rules: NULL skips one, host or
+ * device memory, device memory written in stream order with no host
+ * synchronisation, outputs overwritten, the whole call one timed launch
+ * inside a gsx_timing_begin region (its memsets and kernels; the upload of
+ * the size planes built from msg_bytes precedes the region).  Integer arithmetic only: bit-identical
+ * from run to run; nothing else on the engine changes.  Works after
+ * gsx_propagate and gsx_prop_begin .. gsx_prop_end for every router, with or
+ * without gsx_gater_enforce, partial subscriptions and fanout publishers.
+ * GSX_ESTATE before any propagation, while a stepped call is in flight, after
+ * a timed call, and when the last call did not track first deliverers
+ * (gsx_prop_set_tracking; RandomSub always keeps them).  GSX_EINVAL on a
+ * range shard, and when (longest row of the overlay) * n_msgs >= 2^32: a u32
+ * node counter could wrap.  A call of no messages, or an engine of no pairs,
+ * writes nothing. */
+#define GSX_TRAFFIC_SENT 0
+#define GSX_TRAFFIC_FIRST 1
+#define GSX_TRAFFIC_DUP 2
+#define GSX_TRAFFIC_INVALID 3
+#define GSX_TRAFFIC_GRAYLISTED 4
+#define GSX_TRAFFIC_COLS 5
+int gsx_prop_traffic(gsx_engine* e, const uint32_t* msg_bytes, uint32_t* msg_copies, uint32_t* node_copies,
+                     uint64_t* node_bytes, uint32_t* pair_copies, uint64_t* pair_bytes);
 /* Whether propagation keeps, per pair, the messages its observer first got
  * from the neighbour (the deliveryRecord's first deliverer, score.go:833-854)
  * for gsx_prop_results' first_from.  On by default.  Off, a call keeps only
