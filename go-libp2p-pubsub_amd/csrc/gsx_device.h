@@ -485,6 +485,28 @@ hipError_t launch_timed_export(const PropState& ps, const TimedState& ts, uint16
 hipError_t launch_timed_stats(const PropState& ps, const TimedState& ts, uint32_t bin_ticks, uint32_t n_bins,
                               uint32_t* hist, uint32_t* node_received, unsigned long long* node_tick_sum,
                               hipStream_t st);
+// gsx_timed_traffic (gsx_timed_traffic.hip): the copies of the last timed call
+// (one per message k sent by v to u at a tick <= max_ticks) by what became of
+// them, their bytes, and both by tick bin (bin of tick t: min(t / bin_ticks,
+// n_bins - 1); SENT and IN_FLIGHT by send tick, the rest by arrival tick).
+// sizes [n_msgs] are the messages' bytes (null: 1 each).  Any output may be
+// null; the launcher overwrites the others (it zeroes what its kernel adds to).
+constexpr uint32_t TT_COLS = 7;  // GSX_TT_COLS
+enum { TT_SENT = 0, TT_FIRST = 1, TT_DUP = 2, TT_INVALID = 3, TT_GRAY = 4, TT_FLIGHT = 5, TT_DUPWIN = 6 };  // GSX_TT_*
+struct TimedTrafficArgs {
+    const uint32_t* sizes;
+    uint32_t bin_ticks, n_bins;      // n_bins <= 1024
+    uint32_t* msg_copies;            // [n_msgs][TT_COLS]
+    uint32_t* node_copies;           // [n_nodes][TT_COLS]
+    unsigned long long* node_bytes;  // [n_nodes][2]: sent, arrived
+    uint32_t* pair_copies;           // [n_pairs]: arrived
+    unsigned long long* pair_bytes;  // [n_pairs]
+    unsigned long long* bin_copies;  // [n_bins][TT_COLS]
+    unsigned long long* bin_bytes;   // [n_bins][2]: sent, arrived
+    unsigned long long* node_peak;   // [n_nodes][2]: the largest bin of the node's sent / arrived bytes
+    uint32_t* node_peak_bin;         // [n_nodes][2]: the lowest bin that holds it
+};
+hipError_t launch_timed_traffic(const PropState& ps, const TimedState& ts, const TimedTrafficArgs& a, hipStream_t st);
 // gsx_score_stats (gsx_score_stats.hip): the selected pairs per score bin
 // (bin(s) = the edges k with !(s < edges[k]): a NaN in the top bin) for the
 // engine, per observer row and per peer, and the lowest selected score that

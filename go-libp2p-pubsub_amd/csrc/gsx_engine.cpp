@@ -472,6 +472,16 @@ struct gsx_engine {
         size_t st_hist_cap = 0;
         uint32_t* st_recv = nullptr;
         unsigned long long* st_sum = nullptr;
+        // gsx_timed_traffic: valid while the latencies are the call's; the sizes on the device and
+        // the device side of outputs that go to host memory, each grown on demand
+        bool lat_kept = false;
+        uint32_t *tt_sizes = nullptr, *tt_msg = nullptr, *tt_node = nullptr, *tt_pair = nullptr, *tt_pkbin = nullptr;
+        unsigned long long *tt_nbytes = nullptr, *tt_pbytes = nullptr, *tt_bins = nullptr, *tt_bbytes = nullptr,
+                           *tt_peak = nullptr;
+        size_t tt_sizes_cap = 0, tt_msg_cap = 0, tt_node_cap = 0, tt_pair_cap = 0, tt_pkbin_cap = 0, tt_nbytes_cap = 0,
+               tt_pbytes_cap = 0, tt_bins_cap = 0, tt_bbytes_cap = 0, tt_peak_cap = 0;
+        std::vector<uint32_t> tt_hsizes;  // (host staging of the sizes, alive until their upload is done)
+        bool tt_sizes_busy = false;
     } tprop;
 
     // the peer gater (gsx_set_gater_params; gsx_gater.hip): device arrays per
@@ -1033,7 +1043,8 @@ void timed_free(gsx_engine* e) {
     auto& T = e->tprop;
     void* pp[] = {T.lat, T.fwd, T.rfwd, T.pin, T.cend, T.chg, T.nchg, T.cent, T.ndirty, T.gray_pairs, T.stats, T.fcnt,
                   T.dcnt, T.icnt, T.ring, T.rocc, T.mark, T.seen, T.origin, T.from, T.vmask, T.arr, T.msgs, T.st_hist,
-                  T.st_recv, T.st_sum};
+                  T.st_recv, T.st_sum, T.tt_sizes, T.tt_msg, T.tt_node, T.tt_pair, T.tt_pkbin, T.tt_nbytes, T.tt_pbytes,
+                  T.tt_bins, T.tt_bbytes, T.tt_peak};
     for (void* p : pp)
         if (p) (void)hipFree(p);
     hipEvent_t ev[2] = {T.ev[0], T.ev[1]};
@@ -4414,6 +4425,7 @@ int gsx_set_link_latency(gsx_engine* e, const uint8_t* ticks, size_t n_pairs) {
     if (!e) return GSX_EINVAL;
     if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
     auto& T = e->tprop;
+    T.lat_kept = false;  // gsx_timed_traffic: the last call's copies travelled over the old latencies
     if (!ticks) {
         HIPCHK(e, hipStreamSynchronize(e->stream));
         if (T.lat) (void)hipFree(T.lat);
@@ -4578,6 +4590,7 @@ int gsx_propagate_timed(gsx_engine* e, const gsx_msg* msgs, size_t m, const gsx_
     T.ts = ts;
     T.have = true;
     T.after = true;
+    T.lat_kept = true;
     if (!P.have_last) P.last = ps;  // (gsx_prop_fold_credits folds with the last call's state)
     hipStream_t st = e->stream;
     HIPCHK(e, hipMemsetAsync(T.ring, 0, 8 * N * W, st));  // slot 0: the sources' rows
@@ -4728,6 +4741,85 @@ int gsx_timed_stats(gsx_engine* e, uint32_t bin_ticks, uint32_t n_bins, uint32_t
         host = true;
     }
     if (host) HIPCHK(e, hipStreamSynchronize(e->stream));
+    return GSX_OK;
+}
+
+int gsx_timed_traffic(gsx_engine* e, const uint32_t* msg_bytes, uint32_t bin_ticks, uint32_t n_bins,
+                      const gsx_timed_traffic_out* out) {
+    static_assert(gsx::TT_COLS == GSX_TT_COLS && gsx::TT_SENT == GSX_TT_SENT && gsx::TT_FIRST == GSX_TT_FIRST &&
+                      gsx::TT_DUP == GSX_TT_DUP && gsx::TT_INVALID == GSX_TT_INVALID &&
+                      gsx::TT_GRAY == GSX_TT_GRAYLISTED && gsx::TT_FLIGHT == GSX_TT_IN_FLIGHT &&
+                      gsx::TT_DUPWIN == GSX_TT_DUP_IN_WINDOW,
+                  "the kernel's columns are the header's");
+    if (!e || !out) return GSX_EINVAL;
+    auto& T = e->tprop;
+    if (e->sharded()) return fail(e, GSX_EINVAL, "timed traffic is counted by unsharded engines only");
+    if (!T.have) return fail(e, GSX_ESTATE, "no gsx_propagate_timed call yet");
+    if (!T.after || e->prop.active)
+        return fail(e, GSX_ESTATE, "the last propagation was not a timed call (gsx_prop_traffic counts its copies)");
+    if (!T.lat_kept) return fail(e, GSX_ESTATE, "the link latencies changed after the timed call");
+    if (bin_ticks == 0 || n_bins == 0 || n_bins > 1024) return fail(e, GSX_EINVAL, "bin_ticks >= 1, 1 <= n_bins <= 1024");
+    const gsx::PropState& ps = T.ps;
+    const size_t m = ps.n_msgs, N = ps.n_nodes, E = e->E;
+    // a node's counter takes at most one copy per (pair of its row, message) and side
+    if ((uint64_t)e->max_deg * m >= (1ull << 32))
+        return fail(e, GSX_EINVAL, "longest row x messages >= 2^32: a u32 node counter could wrap");
+    if (m == 0 || E == 0 || N == 0) return GSX_OK;
+    if (!out->msg_copies && !out->node_copies && !out->node_bytes && !out->pair_copies && !out->pair_bytes &&
+        !out->bin_copies && !out->bin_bytes && !out->node_peak && !out->node_peak_bin)
+        return GSX_OK;
+    typedef unsigned long long ull;
+    gsx::TimedTrafficArgs a{};
+    a.bin_ticks = bin_ticks;
+    a.n_bins = n_bins;
+    const size_t K = gsx::TT_COLS;
+    int rc = 0;
+    if ((rc = traffic_out(e, out->msg_copies, &T.tt_msg, &T.tt_msg_cap, m * K, &a.msg_copies)) ||
+        (rc = traffic_out(e, out->node_copies, &T.tt_node, &T.tt_node_cap, N * K, &a.node_copies)) ||
+        (rc = traffic_out(e, reinterpret_cast<ull*>(out->node_bytes), &T.tt_nbytes, &T.tt_nbytes_cap, 2 * N, &a.node_bytes)) ||
+        (rc = traffic_out(e, out->pair_copies, &T.tt_pair, &T.tt_pair_cap, E, &a.pair_copies)) ||
+        (rc = traffic_out(e, reinterpret_cast<ull*>(out->pair_bytes), &T.tt_pbytes, &T.tt_pbytes_cap, E, &a.pair_bytes)) ||
+        (rc = traffic_out(e, reinterpret_cast<ull*>(out->bin_copies), &T.tt_bins, &T.tt_bins_cap, n_bins * K, &a.bin_copies)) ||
+        (rc = traffic_out(e, reinterpret_cast<ull*>(out->bin_bytes), &T.tt_bbytes, &T.tt_bbytes_cap, 2 * (size_t)n_bins,
+                          &a.bin_bytes)) ||
+        (rc = traffic_out(e, reinterpret_cast<ull*>(out->node_peak), &T.tt_peak, &T.tt_peak_cap, 2 * N, &a.node_peak)) ||
+        (rc = traffic_out(e, out->node_peak_bin, &T.tt_pkbin, &T.tt_pkbin_cap, 2 * N, &a.node_peak_bin)))
+        return rc;
+    if (msg_bytes) {
+        if (T.tt_sizes_busy) HIPCHK(e, hipStreamSynchronize(e->stream));  // (the last upload may still read them)
+        T.tt_sizes_busy = false;
+        T.tt_hsizes.assign(msg_bytes, msg_bytes + m);
+        if ((rc = traffic_grow(e, &T.tt_sizes, &T.tt_sizes_cap, m))) return rc;
+        HIPCHK(e, hipMemcpyAsync(T.tt_sizes, T.tt_hsizes.data(), 4 * m, hipMemcpyHostToDevice, e->stream));
+        T.tt_sizes_busy = true;
+        a.sizes = T.tt_sizes;
+    }
+    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
+    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    HIPCHK(e, gsx::launch_timed_traffic(ps, T.ts, a, e->stream));
+    if (region) {
+        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
+        ++e->t_used;
+    }
+    bool host = false;
+    auto back = [&](void* user, const void* dev, size_t bytes) -> hipError_t {
+        if (!user || user == dev) return hipSuccess;
+        host = true;
+        return hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, e->stream);
+    };
+    HIPCHK(e, back(out->msg_copies, a.msg_copies, 4 * m * K));
+    HIPCHK(e, back(out->node_copies, a.node_copies, 4 * N * K));
+    HIPCHK(e, back(out->node_bytes, a.node_bytes, 8 * 2 * N));
+    HIPCHK(e, back(out->pair_copies, a.pair_copies, 4 * E));
+    HIPCHK(e, back(out->pair_bytes, a.pair_bytes, 8 * E));
+    HIPCHK(e, back(out->bin_copies, a.bin_copies, 8 * n_bins * K));
+    HIPCHK(e, back(out->bin_bytes, a.bin_bytes, 8 * 2 * (size_t)n_bins));
+    HIPCHK(e, back(out->node_peak, a.node_peak, 8 * 2 * N));
+    HIPCHK(e, back(out->node_peak_bin, a.node_peak_bin, 4 * 2 * N));
+    if (host) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        T.tt_sizes_busy = false;
+    }
     return GSX_OK;
 }
 

@@ -308,6 +308,27 @@ class TimedOut(C.Structure):
                     dup_in_window=self.dup_in_window, last_tick=self.last_tick, ticks_run=self.ticks_run)
 
 
+# gsx_timed_traffic's columns
+(GSX_TT_SENT, GSX_TT_FIRST, GSX_TT_DUP, GSX_TT_INVALID, GSX_TT_GRAYLISTED, GSX_TT_IN_FLIGHT,
+ GSX_TT_DUP_IN_WINDOW) = range(7)
+GSX_TT_COLS = 7
+
+
+class TimedTrafficOut(C.Structure):
+    """gsx_timed_traffic_out: host or device addresses, None / 0 skips an output"""
+    _fields_ = [
+        ("msg_copies", C.c_void_p),
+        ("node_copies", C.c_void_p),
+        ("node_bytes", C.c_void_p),
+        ("pair_copies", C.c_void_p),
+        ("pair_bytes", C.c_void_p),
+        ("bin_copies", C.c_void_p),
+        ("bin_bytes", C.c_void_p),
+        ("node_peak", C.c_void_p),
+        ("node_peak_bin", C.c_void_p),
+    ]
+
+
 class Msg(C.Structure):
     _fields_ = [("source", C.c_uint32), ("validation", C.c_uint32), ("msg_id", C.c_uint64)]
 
@@ -607,6 +628,8 @@ SIGNATURES = {
     "gsx_timed_results": (C.c_int, [C.c_void_p, P(C.c_uint16), P(C.c_int32)]),
     # (host or device pointers, like gsx_prop_stats: passed as addresses)
     "gsx_timed_stats": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (msg_bytes: host; the struct's outputs host or device pointers)
+    "gsx_timed_traffic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(TimedTrafficOut)]),
     "gsx_score_stats_edges": (C.c_int, [C.c_void_p, P(ScoreStatsSpec)]),
     "gsx_score_stats": (C.c_int, [C.c_void_p, P(ScoreStatsSpec), P(ScoreStatsOut)]),
     "gsx_prop_set_tracking": (C.c_int, [C.c_void_p, C.c_uint32]),

@@ -199,6 +199,114 @@ class PropTraffic:
                            add("pair_bytes", np.uint64))
 
 
+class TimedTraffic:
+    """What a timed propagation cost, and when (gsx_timed_traffic).  A copy is message k sent by
+    v to u at a tick <= max_ticks.  The columns are SENT (every copy), the classes FIRST, DUP,
+    INVALID, GRAYLISTED (arrived: what u's router did with it) and IN_FLIGHT (not arrived when the
+    call ended), and DUP_IN_WINDOW (the DUP copies inside the P3 window; not a class).
+    msg[k, c]: copies of message k; node[u, SENT / IN_FLIGHT]: copies u sent, node[u, c]
+    otherwise: copies that reached u; node_bytes[u] = (bytes u sent, bytes that reached u);
+    pair[q] / pair_bytes[q]: the arrived copies pair q's neighbour sent its observer;
+    bins[b, c] / bin_bytes[b] = (sent, arrived): the same per tick bin (SENT and IN_FLIGHT by
+    send tick, the rest by arrival tick; bin of tick t: min(t // bin_ticks, n_bins - 1));
+    node_peak[u] = (largest bytes u sent in one bin, largest bytes that reached u in one bin),
+    node_peak_bin[u]: the lowest bins that hold them.  Any table may be None (not asked for).
+    Numpy on those integers; nothing here touches the device."""
+
+    SENT, FIRST, DUP, INVALID, GRAYLISTED, IN_FLIGHT, DUP_IN_WINDOW = range(abi.GSX_TT_COLS)
+    COLS = abi.GSX_TT_COLS
+
+    def __init__(self, msg=None, node=None, node_bytes=None, pair=None, pair_bytes=None, bins=None, bin_bytes=None,
+                 node_peak=None, node_peak_bin=None, bin_ticks=1, tick_ns=None):
+        def arr(x, dt, shape):
+            return None if x is None else np.ascontiguousarray(x, dtype=dt).reshape(shape)
+
+        self.msg = arr(msg, np.uint32, (-1, self.COLS))
+        self.node = arr(node, np.uint32, (-1, self.COLS))
+        self.node_bytes = arr(node_bytes, np.uint64, (-1, 2))
+        self.pair = arr(pair, np.uint32, (-1,))
+        self.pair_bytes = arr(pair_bytes, np.uint64, (-1,))
+        self.bins = arr(bins, np.uint64, (-1, self.COLS))
+        self.bin_bytes = arr(bin_bytes, np.uint64, (-1, 2))
+        self.node_peak = arr(node_peak, np.uint64, (-1, 2))
+        self.node_peak_bin = arr(node_peak_bin, np.uint32, (-1, 2))
+        self.bin_ticks = int(bin_ticks)
+        if self.bin_ticks < 1:
+            raise ValueError("bin_ticks >= 1")
+        self.tick_ns = tick_ns
+
+    def total(self, col: int) -> int:
+        """Copies of a column over the whole call (from the per-message table, else the per-bin
+        one, else the per-node one)."""
+        t = self.msg if self.msg is not None else self.bins if self.bins is not None else self.node
+        return int(t[:, col].astype(np.int64).sum())
+
+    def sent(self) -> int:
+        """Every copy of the call: gsx_timed_out.transmissions + in_flight()."""
+        return self.total(self.SENT)
+
+    def in_flight(self) -> int:
+        """Copies sent and not arrived when the call ended."""
+        return self.total(self.IN_FLIGHT)
+
+    def amplification(self) -> np.ndarray:
+        """[m] f64: copies sent per first receipt of the message, SENT / max(FIRST + INVALID, 1)."""
+        t = self.msg.astype(np.int64)
+        return t[:, self.SENT] / np.maximum(t[:, self.FIRST] + t[:, self.INVALID], 1)
+
+    def duplicate_ratio(self) -> np.ndarray:
+        """[n] f64: the share of the copies that reached a node which it had already seen (0 where none did)."""
+        t = self.node.astype(np.int64)
+        got = t[:, self.FIRST:self.GRAYLISTED + 1].sum(1)
+        return np.where(got > 0, t[:, self.DUP] / np.maximum(got, 1), 0.0)
+
+    def upload_bytes(self) -> np.ndarray:
+        return self.node_bytes[:, 0]
+
+    def download_bytes(self) -> np.ndarray:
+        return self.node_bytes[:, 1]
+
+    def load(self, unit: str = "bytes") -> np.ndarray:
+        """[n_bins, 2] u64: the network's load per bin as (sent, arrived), in "bytes" or "copies"."""
+        if unit == "bytes":
+            return self.bin_bytes
+        if unit == "copies":
+            b = self.bins
+            return np.stack([b[:, self.SENT], b[:, self.FIRST:self.GRAYLISTED + 1].sum(1, dtype=np.uint64)], 1)
+        raise ValueError(f"load in {unit!r}")
+
+    def peak_upload(self) -> np.ndarray:
+        """[n] u64: the most bytes each node sent in one bin."""
+        return self.node_peak[:, 0]
+
+    def peak_download(self) -> np.ndarray:
+        """[n] u64: the most bytes that reached each node in one bin."""
+        return self.node_peak[:, 1]
+
+    def busiest(self, k: int, by: str = "upload_bytes") -> np.ndarray:
+        """The k node ids with the largest `by` ("upload_bytes", "download_bytes", "peak_upload",
+        "peak_download", "sent" or "received" copies), largest first, ties broken by ascending id."""
+        if by in ("upload_bytes", "download_bytes", "peak_upload", "peak_download"):
+            key = getattr(self, by)()
+        elif by == "sent":
+            key = self.node[:, self.SENT]
+        elif by == "received":
+            key = self.node[:, self.FIRST:self.GRAYLISTED + 1].astype(np.int64).sum(1)
+        else:
+            raise ValueError(f"busiest by {by!r}")
+        # ascending by (key, -id), reversed: key descending, equal keys by ascending id
+        order = np.lexsort((-np.arange(len(key), dtype=np.int64), key))[::-1]
+        return order[: max(int(k), 0)].astype(np.int64)
+
+    def bytes_per_second(self, per_bin, tick_ns=None) -> np.ndarray:
+        """A per-bin figure (load(), a peak) -> per second: a bin lasts bin_ticks * tick_ns ns
+        (tick_ns: the call's tick length, taken from the call when not given)."""
+        t = self.tick_ns if tick_ns is None else tick_ns
+        if not t or t <= 0:
+            raise ValueError("tick_ns (the call's tick length) is needed")
+        return np.asarray(per_bin, dtype=np.float64) / (self.bin_ticks * float(t) * 1e-9)
+
+
 class TimedStats:
     """Per-message arrival-time summary of a timed propagation (gsx_timed_stats):
     tick_hist[k, b] = nodes whose arrival tick a of message k has min(a // bin_ticks,
@@ -554,6 +662,7 @@ class Engine:
         self._chk(self.lib.gsx_propagate_timed(self.h, ms.ctypes.data_as(C.c_void_p), len(ms), C.byref(cfg),
                                                int(max_ticks), C.byref(out)), "gsx_propagate_timed")
         self._tick_ns = int(cfg.hop_latency_ns)
+        self._timed_m = len(ms)
         tick = frm = None
         if want_results:
             tick, frm = self.timed_results(len(ms))
@@ -586,6 +695,60 @@ class Engine:
                                            C.c_void_p(tsum.ctypes.data if per_node and tsum.size else None)),
                   "gsx_timed_stats")
         return TimedStats(hist, bin_ticks, recv, tsum, getattr(self, "_tick_ns", None))
+
+    _TT_OUTPUTS = ("msg", "node", "node_bytes", "pair", "pair_bytes", "bins", "bin_bytes", "node_peak", "node_peak_bin")
+
+    def timed_traffic(self, n_msgs: int, msg_bytes=None, bin_ticks: int = 1, n_bins: int = 64, per_node: bool = True,
+                      per_pair: bool = False, per_bin: bool = True, outputs=None, out_ptrs=None):
+        """gsx_timed_traffic of the last timed call (n_msgs: its messages) -> TimedTraffic: msg
+        [m, 7] u32; with per_node, node [n, 7] u32 and node_bytes [n, 2] u64; with per_pair, pair
+        [n_pairs] u32 and pair_bytes [n_pairs] u64; with per_bin, bins [n_bins, 7] u64 and bin_bytes
+        [n_bins, 2] u64; with per_node and per_bin, node_peak [n, 2] u64 and node_peak_bin [n, 2]
+        u32.  msg_bytes: [m] u32 sizes (None: 1 byte each, so bytes == copies).  outputs: the
+        names of the tables wanted (of TimedTraffic's attributes), instead of the per_* switches.
+
+        out_ptrs = the nine outputs in that order, or a dict by name: device pointers or tensors
+        (None / 0 skips one) written in stream order with no host sync; then -> None."""
+        last = getattr(self, "_timed_m", None)
+        if last is not None and int(n_msgs) != last:
+            raise ValueError(f"n_msgs is {n_msgs}, the last timed call had {last} messages")
+        sizes = None
+        if msg_bytes is not None:
+            sizes = np.ascontiguousarray(msg_bytes, dtype=np.uint32)
+            if sizes.shape != (n_msgs,):
+                raise ValueError("msg_bytes holds one size per message of the call")
+        sp = C.c_void_p(sizes.ctypes.data if sizes is not None and sizes.size else None)
+        names = self._TT_OUTPUTS
+        o = abi.TimedTrafficOut()
+        fields = [f for f, _ in abi.TimedTrafficOut._fields_]
+        if out_ptrs is not None:
+            ptrs = [out_ptrs.get(k) for k in names] if isinstance(out_ptrs, dict) else list(out_ptrs)
+            if len(ptrs) != len(names):
+                raise ValueError("out_ptrs holds the nine outputs")
+            for f, p in zip(fields, ptrs):
+                setattr(o, f, self._p(p) if p is not None else None)
+            self._chk(self.lib.gsx_timed_traffic(self.h, sp, int(bin_ticks), int(n_bins), C.byref(o)), "gsx_timed_traffic")
+            return None
+        if outputs is None:
+            want = {"msg"}
+            want |= {"node", "node_bytes"} if per_node else set()
+            want |= {"pair", "pair_bytes"} if per_pair else set()
+            want |= {"bins", "bin_bytes"} if per_bin else set()
+            want |= {"node_peak", "node_peak_bin"} if per_node and per_bin else set()
+        else:
+            want = set(outputs)
+            if not want <= set(names):
+                raise ValueError(f"outputs are of {names}")
+        n, E, K, B = self.n_nodes, self.n_pairs, abi.GSX_TT_COLS, max(int(n_bins), 0)
+        spec = {"msg": ((n_msgs, K), np.uint32), "node": ((n, K), np.uint32), "node_bytes": ((n, 2), np.uint64),
+                "pair": ((E,), np.uint32), "pair_bytes": ((E,), np.uint64), "bins": ((B, K), np.uint64),
+                "bin_bytes": ((B, 2), np.uint64), "node_peak": ((n, 2), np.uint64), "node_peak_bin": ((n, 2), np.uint32)}
+        arrs = {k: np.zeros(*spec[k]) if k in want else None for k in names}
+        for f, k in zip(fields, names):
+            a = arrs[k]
+            setattr(o, f, a.ctypes.data if a is not None and a.size else None)
+        self._chk(self.lib.gsx_timed_traffic(self.h, sp, int(bin_ticks), int(n_bins), C.byref(o)), "gsx_timed_traffic")
+        return TimedTraffic(*[arrs[k] for k in names], bin_ticks=bin_ticks, tick_ns=getattr(self, "_tick_ns", None))
 
     def prop_duplicates(self, n_msgs: int) -> np.ndarray:
         """gsx_prop_duplicates: [n_pairs, ceil(m / 64)] u64, bit m of row q = the

@@ -775,6 +775,86 @@ int gsx_timed_results(gsx_engine* e, uint16_t* tick, int32_t* first_from);
  * output, device outputs are written in stream order with no host sync. */
 int gsx_timed_stats(gsx_engine* e, uint32_t bin_ticks, uint32_t n_bins, uint32_t* msg_tick_hist,
                     uint32_t* node_received, uint64_t* node_tick_sum);
+/* What the last timed call cost, and when: the timed twin of gsx_prop_traffic,
+ * reduced on the device from what the call left there.  A copy is message k
+ * sent by v to u.  v sends k at tick f: 0 if v is k's source, else
+ * a(k, v) + vd (a: the tick gsx_timed_results reports).  Apart from
+ * f <= max_ticks the copy exists iff
+ *   - v holds k;
+ *   - k is ACCEPT, or v is its source (a non-accepted message travels one link);
+ *   - v's pair (v -> u) carried the needed eligibility bit in that call: PUBLISH
+ *     for v's own messages, FORWARD otherwise (an unjoined publisher's fanout
+ *     as in the timed call).  The bits are the ones the call worked with: a
+ *     GSX_CREDIT_NOW fold that moved a score afterwards changes nothing here;
+ *   - u is not the peer v first got k from;
+ *   - u is not k's origin.
+ * It arrives at f + lat[(u -> v)].  With f <= max_ticks the copy is SENT and
+ * falls in exactly one of five classes:
+ *   GSX_TT_SENT           every copy with f <= max_ticks
+ *   GSX_TT_FIRST          arrived; u's first receipt of an ACCEPT message
+ *   GSX_TT_DUP            arrived; u had seen k (a copy of the same tick from a
+ *                         higher-indexed sender included)
+ *   GSX_TT_INVALID        arrived; u's first receipt of a REJECT / IGNORE /
+ *                         THROTTLE message
+ *   GSX_TT_GRAYLISTED     arrived; dropped by u's AcceptFrom
+ *   GSX_TT_IN_FLIGHT      f <= max_ticks < f + lat: sent, not arrived when the
+ *                         call ended
+ *   GSX_TT_DUP_IN_WINDOW  not a class: the DUP copies with
+ *                         arrival - a(k, u) <= lim, the P3 window of the call
+ * A node whose send tick lies beyond max_ticks has sent nothing.  Over every
+ * table that has the columns, SENT == FIRST + DUP + INVALID + GRAYLISTED +
+ * IN_FLIGHT; SENT - IN_FLIGHT is gsx_timed_out.transmissions; FIRST, DUP,
+ * INVALID, GRAYLISTED and DUP_IN_WINDOW are its deliveries, duplicates,
+ * rejected + ignored, graylisted and dup_in_window.
+ *   msg_copies[k * GSX_TT_COLS + c]   copies of message k in column c
+ *   node_copies[u * GSX_TT_COLS + c]  c = SENT, IN_FLIGHT: copies u sent; else:
+ *                                     copies of column c that reached u
+ *   node_bytes[2 u], [2 u + 1]        bytes u sent (in flight included); bytes
+ *                                     that reached u (the four arrived classes)
+ *   pair_copies[q], pair_bytes[q]     q = (u -> v): the copies v sent u that
+ *                                     arrived (four classes), their bytes
+ *   bin_copies[b * GSX_TT_COLS + c]   SENT and IN_FLIGHT by send tick, the
+ *                                     other columns by arrival tick
+ *   bin_bytes[2 b], [2 b + 1]         bytes sent in the bin; bytes that arrived
+ *   node_peak[2 u], [2 u + 1]         the largest, over the bins, of the bytes u
+ *                                     sent / that reached u in one bin
+ *   node_peak_bin[2 u], [2 u + 1]     the lowest bin that attains it (0 when
+ *                                     the peak is 0)
+ * The bin of tick t is min(t / bin_ticks, n_bins - 1), gsx_timed_stats' rule
+ * (bin_ticks >= 1, 1 <= n_bins <= 1024).  msg_bytes is host memory: the sizes
+ * of the last timed call's n_msgs messages (any u32); NULL counts 1 byte per
+ * message, so bytes == copies.  The outputs follow gsx_prop_traffic's and
+ * gsx_timed_stats' rules: NULL skips one, host or device memory, device
+ * memory written in stream order with no host synchronisation, outputs
+ * overwritten, the whole call one timed launch inside a gsx_timing_begin
+ * region (the upload of the sizes precedes it).  Integer arithmetic only:
+ * bit-identical from run to run; nothing else on the engine changes.
+ * GSX_ESTATE before any timed call, when the last propagation-type call was
+ * not a timed one (gsx_propagate, gsx_prop_begin .. gsx_prop_end), after
+ * gsx_set_link_latency, and after an overlay load.  GSX_EINVAL for bad bins,
+ * on a range shard, and when (longest row of the overlay) * n_msgs >= 2^32.
+ * A call of no messages, or an engine of no pairs, writes nothing. */
+#define GSX_TT_SENT 0
+#define GSX_TT_FIRST 1
+#define GSX_TT_DUP 2
+#define GSX_TT_INVALID 3
+#define GSX_TT_GRAYLISTED 4
+#define GSX_TT_IN_FLIGHT 5
+#define GSX_TT_DUP_IN_WINDOW 6
+#define GSX_TT_COLS 7
+typedef struct gsx_timed_traffic_out { /* every pointer: NULL skips it; host or device memory */
+    uint32_t* msg_copies;    /* [n_msgs][GSX_TT_COLS] */
+    uint32_t* node_copies;   /* [n_nodes][GSX_TT_COLS] */
+    uint64_t* node_bytes;    /* [n_nodes][2] */
+    uint32_t* pair_copies;   /* [n_pairs] */
+    uint64_t* pair_bytes;    /* [n_pairs] */
+    uint64_t* bin_copies;    /* [n_bins][GSX_TT_COLS] */
+    uint64_t* bin_bytes;     /* [n_bins][2] */
+    uint64_t* node_peak;     /* [n_nodes][2] */
+    uint32_t* node_peak_bin; /* [n_nodes][2] */
+} gsx_timed_traffic_out;
+int gsx_timed_traffic(gsx_engine* e, const uint32_t* msg_bytes, uint32_t bin_ticks, uint32_t n_bins,
+                      const gsx_timed_traffic_out* out);
 
 /* Orders the engine's work on a caller's HIP stream (hipStream_t; NULL = the
  * engine's own), e.g. torch's current stream, so that its kernels and the
