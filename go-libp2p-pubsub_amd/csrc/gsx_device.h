@@ -537,6 +537,33 @@ hipError_t launch_score_stats_fill(unsigned long long* obs_min, uint64_t n_obs, 
 hipError_t launch_score_stats(const ScoreStatsArgs& a, hipStream_t st);
 hipError_t launch_score_stats_unkey(unsigned long long* obs_min, uint64_t n_obs, unsigned long long* peer_min,
                                     uint64_t n_peer, hipStream_t st);
+// gsx_score_parts (gsx_score_parts.hip): what score() adds up for each pair
+// (SP_PARTS doubles: the weighted P1 .. P4 summed over the scored topics, P5,
+// P6, P7, the capped topic sum and the score), the part that is lowest and
+// negative (its cause), the topic whose weighted score is (its worst topic),
+// and the selected pairs counted per (score bin, cause), per (score bin, worst
+// topic), per (observer row, cause) and per (peer, cause).  Selection and bins
+// are gsx_score_stats's.  Any output may be null; the counters are added to
+// (the caller zeroes them).
+constexpr uint32_t SP_P1 = 0, SP_P2 = 1, SP_P3 = 2, SP_P3B = 3, SP_P4 = 4, SP_P5 = 5, SP_P6 = 6, SP_P7 = 7,
+                   SP_TOPICS = 8, SP_SCORE = 9, SP_PARTS = 10;  // GSX_PART_*
+constexpr uint32_t SP_CAUSE_NONE = 8, SP_CAUSES = 9;            // GSX_CAUSE_*
+constexpr uint32_t SP_TOPIC_NONE = 0xFFu;                       // GSX_TOPIC_NONE
+constexpr uint32_t SP_MAX_TOPICS = 64;                          // GSX_MAX_TOPICS
+struct ScorePartsArgs {
+    const uint32_t* pair_obs;  // per pair: local observer index
+    const int32_t* col;        // per pair: the peer's global node id
+    uint32_t select, topic, n_edges;
+    double edges[SS_MAX_EDGES];
+    double* pair_parts;              // [n_pairs][SP_PARTS]
+    uint8_t* pair_cause;             // [n_pairs]
+    uint8_t* pair_topic;             // [n_pairs]
+    unsigned long long* cause_hist;  // [n_edges + 1][SP_CAUSES]
+    unsigned long long* topic_hist;  // [n_edges + 1][n_topics + 1]
+    uint32_t* obs_cause;             // [n_local][SP_CAUSES]
+    uint32_t* peer_cause;            // [n_total][SP_CAUSES]
+};
+hipError_t launch_score_parts(const DevState& s, const KernParams& kp, const ScorePartsArgs& a, hipStream_t st);
 // The peer gater (gsx_gater.hip; peer_gater.go).  Per observer: validate,
 // throttle, last_throttle and the `hot` byte of the last gsx_accept_from (quiet
 // period, throttle and ratio all say "gate on").  Per group g (an (observer, IP)

@@ -443,6 +443,9 @@ struct gsx_engine {
         unsigned long long* ss_hist = nullptr;
         uint32_t *ss_obs_bins = nullptr, *ss_peer_bins = nullptr;
         unsigned long long *ss_obs_min = nullptr, *ss_peer_min = nullptr;
+        // gsx_score_parts: the same for its four tables (the pair outputs are staged per call)
+        unsigned long long *sp_cause_hist = nullptr, *sp_topic_hist = nullptr;
+        uint32_t *sp_obs_cause = nullptr, *sp_peer_cause = nullptr;
     } prop;
     bool prop_track = true;  // gsx_prop_set_tracking: keep first-deliverer rows (gsx_prop_results)
 
@@ -1107,7 +1110,8 @@ void free_state(gsx_engine* e) {
                   e->prop.st_hist, e->prop.st_recv, e->prop.st_sum,
                   e->prop.tr_sset, e->prop.tr_planes, e->prop.tr_msg, e->prop.tr_node, e->prop.tr_pair,
                   e->prop.tr_nbytes, e->prop.tr_pbytes,
-                  e->prop.ss_hist, e->prop.ss_obs_bins, e->prop.ss_peer_bins, e->prop.ss_obs_min, e->prop.ss_peer_min};
+                  e->prop.ss_hist, e->prop.ss_obs_bins, e->prop.ss_peer_bins, e->prop.ss_obs_min, e->prop.ss_peer_min,
+                  e->prop.sp_cause_hist, e->prop.sp_topic_hist, e->prop.sp_obs_cause, e->prop.sp_peer_cause};
     for (void* p : pp)
         if (p) (void)hipFree(p);
     std::vector<hipEvent_t> evs = std::move(e->prop.ev);
@@ -1975,7 +1979,7 @@ int load_overlay(gsx_engine* e, uint32_t n_total, uint32_t node_lo, uint32_t n_n
         (rc = dalloc(e, &e->d_bp, e->rs)) || (rc = dalloc(e, &e->d_app, e->rs)) ||
         (rc = dalloc(e, &e->d_score, e->rs)) || (rc = dalloc(e, &e->d_ipg, 2 * e->rs)) ||
         (rc = dalloc(e, &e->d_ipcount, e->n_groups)) || (rc = dalloc(e, &e->d_col, E)) ||
-        (rc = dalloc(e, &e->d_backoff, (size_t)e->T * E)) ||
+        (rc = dalloc(e, &e->d_backoff, (size_t)e->T * (E ? E : 1))) ||
         (rc = dalloc(e, &e->d_bo8, (size_t)((e->T + 7) / 8) * E + 4))) {
         free_state(e);
         return rc;
@@ -4912,6 +4916,107 @@ int gsx_score_stats(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_s
     if (h_pm) HIPCHK(e, hipMemcpyAsync(out->peer_min, d_pm, 8 * NT, hipMemcpyDeviceToHost, e->stream));
     if (h_hist || h_ob || h_om || h_pb || h_pm) HIPCHK(e, hipStreamSynchronize(e->stream));
     return GSX_OK;
+}
+
+int gsx_score_parts(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_score_parts_out* out) {
+    static_assert(gsx::SP_PARTS == GSX_PARTS && gsx::SP_CAUSES == GSX_CAUSES && gsx::SP_CAUSE_NONE == GSX_CAUSE_NONE &&
+                      gsx::SP_TOPIC_NONE == GSX_TOPIC_NONE && gsx::SP_MAX_TOPICS == GSX_MAX_TOPICS &&
+                      gsx::SP_P1 == GSX_PART_P1 && gsx::SP_P2 == GSX_PART_P2 && gsx::SP_P3 == GSX_PART_P3 &&
+                      gsx::SP_P3B == GSX_PART_P3B && gsx::SP_P4 == GSX_PART_P4 && gsx::SP_P5 == GSX_PART_P5 &&
+                      gsx::SP_P6 == GSX_PART_P6 && gsx::SP_P7 == GSX_PART_P7 && gsx::SP_TOPICS == GSX_PART_TOPICS &&
+                      gsx::SP_SCORE == GSX_PART_SCORE,
+                  "the kernel's constants are the header's");
+    if (!e || !spec || !out) return GSX_EINVAL;
+    if (spec->select > GSX_SS_MESH) return fail(e, GSX_EINVAL, "unknown selection");
+    if (spec->n_edges > GSX_SS_MAX_EDGES) return fail(e, GSX_EINVAL, "more than GSX_SS_MAX_EDGES edges");
+    for (uint32_t k = 0; k < spec->n_edges; ++k)
+        if (invalid_number(spec->edges[k]) || (k && !(spec->edges[k] > spec->edges[k - 1])))
+            return fail(e, GSX_EINVAL, "edges must be finite and strictly ascending");
+    if (spec->select == GSX_SS_MESH && spec->topic >= e->T) return fail(e, GSX_EINVAL, "topic out of range");
+    if (int rc = gx_busy(e)) return rc;  // (before the shard test: only a range shard can have one in flight)
+    if (e->sharded()) return fail(e, GSX_EINVAL, "gsx_score_parts is not offered on a range shard");
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    if (!out->pair_parts && !out->pair_cause && !out->pair_topic && !out->cause_hist && !out->topic_hist &&
+        !out->obs_cause && !out->peer_cause)
+        return GSX_OK;
+    if (e->E)  // (an engine of no pairs has nothing to settle: its tables are zeroed below)
+        if (int rc = ensure_scores(e)) return rc;
+    auto& P = e->prop;
+    const size_t nb = (size_t)spec->n_edges + 1, NL = e->n_nodes, NT = e->n_total, E = e->E, ntc = (size_t)e->T + 1;
+    constexpr size_t NC = GSX_CAUSES, MAXB = gsx::SS_MAX_BINS;
+    // device memory is written in place, in stream order; host memory gets a copy of the engine's
+    // buffers (the tables) or of a buffer of this call (the pair outputs)
+    const bool h_pp = out->pair_parts && E && !on_device(out->pair_parts),
+               h_pc = out->pair_cause && E && !on_device(out->pair_cause),
+               h_pt = out->pair_topic && E && !on_device(out->pair_topic),
+               h_ch = out->cause_hist && !on_device(out->cause_hist),
+               h_th = out->topic_hist && !on_device(out->topic_hist),
+               h_oc = out->obs_cause && NL && !on_device(out->obs_cause),
+               h_pe = out->peer_cause && NT && !on_device(out->peer_cause);
+    if (h_ch && !P.sp_cause_hist)
+        if (int rc = dalloc(e, &P.sp_cause_hist, MAXB * NC)) return rc;
+    if (h_th && !P.sp_topic_hist)
+        if (int rc = dalloc(e, &P.sp_topic_hist, MAXB * (GSX_MAX_TOPICS + 1))) return rc;
+    if (h_oc && !P.sp_obs_cause)
+        if (int rc = dalloc(e, &P.sp_obs_cause, NL * NC)) return rc;
+    if (h_pe && !P.sp_peer_cause)
+        if (int rc = dalloc(e, &P.sp_peer_cause, NT * NC)) return rc;
+    double* t_pp = nullptr;
+    uint8_t *t_pc = nullptr, *t_pt = nullptr;
+    auto drop = [&]() {
+        for (void* p : {(void*)t_pp, (void*)t_pc, (void*)t_pt})
+            if (p) (void)hipFree(p);
+    };
+    int rc = GSX_OK;
+    if (h_pp) rc = dalloc(e, &t_pp, E * GSX_PARTS);
+    if (!rc && h_pc) rc = dalloc(e, &t_pc, E);
+    if (!rc && h_pt) rc = dalloc(e, &t_pt, E);
+    if (rc) {
+        drop();
+        return rc;
+    }
+    using u64p = unsigned long long*;
+    gsx::ScorePartsArgs a{};
+    a.pair_obs = e->d_pair_obs;
+    a.col = e->d_col;
+    a.select = spec->select;
+    a.topic = spec->select == GSX_SS_MESH ? spec->topic : 0;
+    a.n_edges = spec->n_edges;
+    for (uint32_t k = 0; k < spec->n_edges; ++k) a.edges[k] = spec->edges[k];
+    a.pair_parts = !E ? nullptr : h_pp ? t_pp : out->pair_parts;
+    a.pair_cause = !E ? nullptr : h_pc ? t_pc : out->pair_cause;
+    a.pair_topic = !E ? nullptr : h_pt ? t_pt : out->pair_topic;
+    a.cause_hist = h_ch ? P.sp_cause_hist : reinterpret_cast<u64p>(out->cause_hist);
+    a.topic_hist = h_th ? P.sp_topic_hist : reinterpret_cast<u64p>(out->topic_hist);
+    a.obs_cause = !NL ? nullptr : h_oc ? P.sp_obs_cause : out->obs_cause;
+    a.peer_cause = !NT ? nullptr : h_pe ? P.sp_peer_cause : out->peer_cause;
+    // (a failed call below leaves the stream's work to finish before the pair buffers go)
+    auto run = [&]() -> int {
+        const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
+        if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+        if (a.cause_hist) HIPCHK(e, hipMemsetAsync(a.cause_hist, 0, 8 * nb * NC, e->stream));
+        if (a.topic_hist) HIPCHK(e, hipMemsetAsync(a.topic_hist, 0, 8 * nb * ntc, e->stream));
+        if (a.obs_cause) HIPCHK(e, hipMemsetAsync(a.obs_cause, 0, 4 * NL * NC, e->stream));
+        if (a.peer_cause) HIPCHK(e, hipMemsetAsync(a.peer_cause, 0, 4 * NT * NC, e->stream));
+        HIPCHK(e, gsx::launch_score_parts(dev_state(e), kern_params(e), a, e->stream));
+        if (region) {
+            HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
+            ++e->t_used;
+        }
+        if (h_pp) HIPCHK(e, hipMemcpyAsync(out->pair_parts, t_pp, 8 * E * GSX_PARTS, hipMemcpyDeviceToHost, e->stream));
+        if (h_pc) HIPCHK(e, hipMemcpyAsync(out->pair_cause, t_pc, E, hipMemcpyDeviceToHost, e->stream));
+        if (h_pt) HIPCHK(e, hipMemcpyAsync(out->pair_topic, t_pt, E, hipMemcpyDeviceToHost, e->stream));
+        if (h_ch) HIPCHK(e, hipMemcpyAsync(out->cause_hist, a.cause_hist, 8 * nb * NC, hipMemcpyDeviceToHost, e->stream));
+        if (h_th) HIPCHK(e, hipMemcpyAsync(out->topic_hist, a.topic_hist, 8 * nb * ntc, hipMemcpyDeviceToHost, e->stream));
+        if (h_oc) HIPCHK(e, hipMemcpyAsync(out->obs_cause, a.obs_cause, 4 * NL * NC, hipMemcpyDeviceToHost, e->stream));
+        if (h_pe) HIPCHK(e, hipMemcpyAsync(out->peer_cause, a.peer_cause, 4 * NT * NC, hipMemcpyDeviceToHost, e->stream));
+        if (h_pp || h_pc || h_pt || h_ch || h_th || h_oc || h_pe) HIPCHK(e, hipStreamSynchronize(e->stream));
+        return GSX_OK;
+    };
+    rc = run();
+    if (rc && (t_pp || t_pc || t_pt)) (void)hipStreamSynchronize(e->stream);
+    drop();
+    return rc;
 }
 
 // ---- the peer gater (peer_gater.go) and AcceptFrom (gossipsub.go:583-594) ------

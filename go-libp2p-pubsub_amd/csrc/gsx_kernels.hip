@@ -17,21 +17,7 @@ namespace gsx {
 
 // ---- hot path: fused refresh + score ---------------------------------------
 
-// x is the same in every lane of the wave: says so to the compiler, which then
-// keeps it (and what is loaded through it) in scalar registers.
-__device__ __forceinline__ uint64_t wave_uniform(uint64_t x) {
-    return (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)x) |
-           (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(x >> 32)) << 32;
-}
-
-// The zero-map bytes of one (tile, topic) at the even byte offset o, MFP's in
-// bits 0-7 and IMD's in bits 8-15, read through their aligned 32-bit word (a
-// scalar load: the offset is wave-uniform).
-constexpr uint32_t ZM_MFP_BITS = 0x00FFu, ZM_IMD_BITS = 0xFF00u;
-__device__ __forceinline__ uint32_t zmap_pair(const uint8_t* zmap, uint64_t o) {
-    const uint32_t w = reinterpret_cast<const uint32_t*>(zmap)[o >> 2];
-    return __builtin_amdgcn_readfirstlane((w >> ((uint32_t)(o & 2) * 8)) & 0xFFFFu);
-}
+// (wave_uniform and zmap_pair: gsx_ops.h, shared with the score-parts pass)
 
 template <int TT, bool REFRESH>
 __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp, int64_t now,

@@ -32,18 +32,36 @@ __device__ __forceinline__ double ip_colocation(const DevState& s, const DevPeer
 // From p5 and p6 as given (p6 is not read when w6 == 0): the refresh pass passes
 // the constant +0.0 for what the pair zero map says is zero, and every product
 // is still executed.
-__device__ __forceinline__ double score_tail_vals(const DevPeerParams& pp, double score, double p5, double p6,
-                                                  double bp) {
+// score_tail_parts is the same with every piece handed to `part` as it is
+// formed (index: gsx_device.h SP_*; SP_TOPICS is the capped topic sum, a term
+// that score() does not add is not handed over): gsx_score_parts reports the
+// very values score() adds.  score_tail_vals is its instance that looks at none.
+template <class F>
+__device__ __forceinline__ double score_tail_parts(const DevPeerParams& pp, double score, double p5, double p6,
+                                                   double bp, F&& part) {
     if (pp.topic_score_cap > 0 && score > pp.topic_score_cap) score = pp.topic_score_cap;
-    score += p5 * pp.w5;
+    part(SP_TOPICS, score);
+    const double t5 = p5 * pp.w5;
+    part(SP_P5, t5);
+    score += t5;
     // With w6 == 0 the term is +-0 and score (never -0) is unchanged.
-    if (pp.w6 != 0.0) score += p6 * pp.w6;
+    if (pp.w6 != 0.0) {
+        const double t6 = p6 * pp.w6;
+        part(SP_P6, t6);
+        score += t6;
+    }
     if (bp > pp.thr7) {
         const double excess = bp - pp.thr7;
         const double p7 = excess * excess;
-        score += p7 * pp.w7;
+        const double t7 = p7 * pp.w7;
+        part(SP_P7, t7);
+        score += t7;
     }
     return score;
+}
+__device__ __forceinline__ double score_tail_vals(const DevPeerParams& pp, double score, double p5, double p6,
+                                                  double bp) {
+    return score_tail_parts(pp, score, p5, p6, bp, [](uint32_t, double) {});
 }
 __device__ __forceinline__ double score_tail(const DevState& s, const DevPeerParams& pp, uint64_t p, double score,
                                              double bp) {
@@ -101,28 +119,47 @@ __host__ __device__ __forceinline__ int64_t div_q1(int64_t mt, int64_t q1, doubl
 // One topic's contribution, score.go:276-311.  P1 and P3 are computed only for
 // the records that have them (in the mesh; active and under the threshold), as
 // the reference does: a record outside the mesh never reaches the division.
-__device__ __forceinline__ double topic_score(const DevTopicParams& tp, uint8_t fl, int64_t mesh_time, double fmd,
-                                              double mmd, double mfp, double imd) {
+// topic_score_parts hands every weighted term to `part` as it is added (index:
+// gsx_device.h SP_P1 .. SP_P4, before the topic weight; a term the record does
+// not have is not handed over): gsx_score_parts reports the very products
+// score() adds.  topic_score is its instance that looks at none.
+template <class F>
+__device__ __forceinline__ double topic_score_parts(const DevTopicParams& tp, uint8_t fl, int64_t mesh_time,
+                                                    double fmd, double mmd, double mfp, double imd, F&& part) {
     double ts = 0.0;
     if (fl & REC_IN_MESH) {  // P1, integer Duration division (:280)
         double p1 = (double)div_q1(mesh_time, tp.q1, tp.inv_q1);
         if (p1 > tp.cap1) p1 = tp.cap1;
-        ts += p1 * tp.w1;
+        const double t1 = p1 * tp.w1;
+        part(SP_P1, t1);
+        ts += t1;
     }
     const double p2 = fmd;  // P2
-    ts += p2 * tp.w2;
+    const double t2 = p2 * tp.w2;
+    part(SP_P2, t2);
+    ts += t2;
     if (fl & REC_ACTIVE) {  // P3
         if (mmd < tp.thr3) {
             const double deficit = tp.thr3 - mmd;
             const double p3 = deficit * deficit;
-            ts += p3 * tp.w3;
+            const double t3 = p3 * tp.w3;
+            part(SP_P3, t3);
+            ts += t3;
         }
     }
     const double p3b = mfp;  // P3b
-    ts += p3b * tp.w3b;
+    const double t3b = p3b * tp.w3b;
+    part(SP_P3B, t3b);
+    ts += t3b;
     const double p4 = (imd * imd);  // P4
-    ts += p4 * tp.w4;
+    const double t4 = p4 * tp.w4;
+    part(SP_P4, t4);
+    ts += t4;
     return ts * tp.topic_weight;
+}
+__device__ __forceinline__ double topic_score(const DevTopicParams& tp, uint8_t fl, int64_t mesh_time, double fmd,
+                                              double mmd, double mfp, double imd) {
+    return topic_score_parts(tp, fl, mesh_time, fmd, mmd, mfp, imd, [](uint32_t, double) {});
 }
 
 // meshTime of a stored record: FRESH (grafted, not refreshed since) -> 0,
@@ -131,6 +168,10 @@ __device__ __forceinline__ int64_t mesh_time_of(const DevState& s, uint8_t fl, u
     if (!(fl & REC_IN_MESH) || (fl & REC_FRESH)) return 0;
     const int64_t graft = reinterpret_cast<const int64_t*>(s.rec)[rec_index(p, t, s.n_topics, GRAFT)];
     return s.last_refresh - graft;
+}
+// The same from a graftTime loaded beforehand (with the record's other fields).
+__device__ __forceinline__ int64_t mesh_time_from(const DevState& s, uint8_t fl, int64_t graft) {
+    return (!(fl & REC_IN_MESH) || (fl & REC_FRESH)) ? 0 : s.last_refresh - graft;
 }
 
 // x *= decay; x = 0 if x < DecayToZero   (score.go:527-542, 553-556)
@@ -144,6 +185,22 @@ __device__ __forceinline__ double decay(double x, double d, double dtz) {
 // the constant: lanes racing on one tile's byte all write the same value.
 __device__ __forceinline__ void zmap_mark(const DevState& s, uint64_t p, uint32_t t, int field) {
     s.zmap[zmap_index(p, t, s.n_topics, field)] = ZM_MAYBE;
+}
+
+// x is the same in every lane of the wave: says so to the compiler, which then
+// keeps it (and what is loaded through it) in scalar registers.
+__device__ __forceinline__ uint64_t wave_uniform(uint64_t x) {
+    return (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)x) |
+           (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(x >> 32)) << 32;
+}
+
+// The zero-map bytes of one (tile, topic) at the even byte offset o, MFP's in
+// bits 0-7 and IMD's in bits 8-15, read through their aligned 32-bit word (a
+// scalar load: the offset is wave-uniform).
+constexpr uint32_t ZM_MFP_BITS = 0x00FFu, ZM_IMD_BITS = 0xFF00u;
+__device__ __forceinline__ uint32_t zmap_pair(const uint8_t* zmap, uint64_t o) {
+    const uint32_t w = reinterpret_cast<const uint32_t*>(zmap)[o >> 2];
+    return __builtin_amdgcn_readfirstlane((w >> ((uint32_t)(o & 2) * 8)) & 0xFFFFu);
 }
 
 // The pair zero map's marks (gsx_device.h), as plain: one tile's entry, and

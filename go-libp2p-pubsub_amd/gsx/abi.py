@@ -437,6 +437,31 @@ class ScoreStatsOut(C.Structure):
     ]
 
 
+# gsx_score_parts: GSX_PART_*, GSX_CAUSE_*, GSX_TOPIC_NONE
+GSX_PART_P1, GSX_PART_P2, GSX_PART_P3, GSX_PART_P3B, GSX_PART_P4 = 0, 1, 2, 3, 4
+GSX_PART_P5, GSX_PART_P6, GSX_PART_P7, GSX_PART_TOPICS, GSX_PART_SCORE = 5, 6, 7, 8, 9
+GSX_PARTS = 10
+GSX_CAUSE_NONE = 8
+GSX_CAUSES = 9
+GSX_TOPIC_NONE = 0xFF
+PART_NAMES = ("p1", "p2", "p3", "p3b", "p4", "p5", "p6", "p7", "topics", "score")
+CAUSE_NAMES = PART_NAMES[:GSX_CAUSE_NONE] + ("none",)
+
+
+class ScorePartsOut(C.Structure):
+    """gsx_score_parts_out: host or device addresses, None skips an output"""
+
+    _fields_ = [
+        ("pair_parts", C.c_void_p),
+        ("pair_cause", C.c_void_p),
+        ("pair_topic", C.c_void_p),
+        ("cause_hist", C.c_void_p),
+        ("topic_hist", C.c_void_p),
+        ("obs_cause", C.c_void_p),
+        ("peer_cause", C.c_void_p),
+    ]
+
+
 # the peer gater (peer_gater.go) and AcceptFrom
 GSX_ACCEPT_NONE = 0
 GSX_ACCEPT_CONTROL = 1
@@ -632,6 +657,7 @@ SIGNATURES = {
     "gsx_timed_traffic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, P(TimedTrafficOut)]),
     "gsx_score_stats_edges": (C.c_int, [C.c_void_p, P(ScoreStatsSpec)]),
     "gsx_score_stats": (C.c_int, [C.c_void_p, P(ScoreStatsSpec), P(ScoreStatsOut)]),
+    "gsx_score_parts": (C.c_int, [C.c_void_p, P(ScoreStatsSpec), P(ScorePartsOut)]),
     "gsx_prop_set_tracking": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_prop_duplicates": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_size_t]),
     # (msg_bytes: host; the outputs host or device pointers, like gsx_prop_stats: passed as addresses)

@@ -452,6 +452,64 @@ class ScoreStats:
                           both(self.peer_min, other.peer_min, np.minimum))
 
 
+class ScoreParts:
+    """What the scores are made of (gsx_score_parts): the selected pairs per (score bin, cause) as
+    cause_hist [B, 9] u64 and per (score bin, worst topic) as topic_hist [B, T + 1] u64 (last
+    column: no topic is negative), per (observer row, cause) as obs_cause [n, 9] u32 and per
+    (peer, cause) as peer_cause [n, 9] u32; B = len(edges) + 1, the bins gsx_score_stats's.  The
+    cause of a pair is the lowest negative one of its parts P1 .. P7 (abi.CAUSE_NAMES; the last:
+    none is negative).  With per_pair: parts [E, 10] f64 (abi.PART_NAMES), cause [E] u8 and
+    worst_topic [E] u8 (abi.GSX_TOPIC_NONE: none).  Any of them may be None.  Everything below is
+    numpy on those tables."""
+
+    def __init__(self, edges, cause_hist=None, topic_hist=None, obs_cause=None, peer_cause=None, parts=None,
+                 cause=None, worst_topic=None):
+        self.edges = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        B, NC = len(self.edges) + 1, abi.GSX_CAUSES
+
+        def arr(a, dtype, *shape):
+            return None if a is None else np.ascontiguousarray(a, dtype=dtype).reshape(*shape)
+
+        self.cause_hist = arr(cause_hist, np.uint64, B, NC)
+        self.topic_hist = arr(topic_hist, np.uint64, B, -1)
+        self.obs_cause = arr(obs_cause, np.uint32, -1, NC)
+        self.peer_cause = arr(peer_cause, np.uint32, -1, NC)
+        self.parts = arr(parts, np.float64, -1, abi.GSX_PARTS)
+        self.cause = arr(cause, np.uint8, -1)
+        self.worst_topic = arr(worst_topic, np.uint8, -1)
+
+    def _bins(self, below) -> int:
+        """The bins under edge `below` (None: all of them)."""
+        if below is None:
+            return len(self.edges) + 1
+        k = np.nonzero(self.edges == below)[0]
+        if len(k) == 0:
+            raise ValueError(f"{below} is not one of the edges {self.edges.tolist()}")
+        return int(k[0]) + 1
+
+    @staticmethod
+    def _cause(cause) -> int:
+        return abi.CAUSE_NAMES.index(cause) if isinstance(cause, str) else int(cause)
+
+    def blame(self, below=None) -> np.ndarray:
+        """[9] i64: the selected pairs with score < below (one of the edges; None: all), per cause."""
+        return self.cause_hist[: self._bins(below)].sum(0, dtype=np.int64)
+
+    def blame_topics(self, below=None) -> np.ndarray:
+        """[T + 1] i64: the same per worst topic; the last entry: no topic is negative."""
+        return self.topic_hist[: self._bins(below)].sum(0, dtype=np.int64)
+
+    def fraction(self, cause, below=None) -> float:
+        """blame(below)[cause] over the selected pairs below the edge; nan if there is none."""
+        b = self.blame(below)
+        tot = int(b.sum())
+        return float(b[self._cause(cause)]) / tot if tot else float("nan")
+
+    def peers_blamed(self, cause) -> np.ndarray:
+        """The nodes with at least one selected observer whose cause is this one, ascending."""
+        return np.nonzero(self.peer_cause[:, self._cause(cause)])[0]
+
+
 class ConnTrim:
     """A forced trim of every observer's connections (gsx_conn_trim): trim[p] = 1
     for the pairs it closes, node_trimmed[u] their number in u's row;
@@ -1168,6 +1226,43 @@ class Engine:
         out = abi.ScoreStatsOut(*[a.ctypes.data if a is not None and a.size else None for a in (hist, ob, om, pb, pm)])
         self._chk(self.lib.gsx_score_stats(self.h, C.byref(sp), C.byref(out)), "gsx_score_stats")
         return ScoreStats(np.array(sp.edges[: B - 1], dtype=np.float64), hist, ob, om, pb, pm)
+
+    def score_parts(self, edges=None, select="present", topic: int = 0, per_pair: bool = False, per_node: bool = True,
+                    out_ptrs=None):
+        """gsx_score_parts -> ScoreParts: which of P1 .. P7 is the lowest negative part of each
+        selected pair's score (its cause) and on which topic its weighted topic score is lowest,
+        counted per score bin over `edges` (None: score_stats_edges()), with per_node per observer
+        row and per peer, with per_pair also the parts, cause and worst topic of every pair.
+
+        out_ptrs = (pair_parts, pair_cause, pair_topic, cause_hist, topic_hist, obs_cause,
+        peer_cause): device pointers or tensors (None / 0 skips one) written in stream order with
+        no host sync, as score_stats takes them; then -> None."""
+        sp = abi.ScoreStatsSpec(select=abi.SS_SELECT[select] if isinstance(select, str) else int(select),
+                                topic=int(topic))
+        if edges is None:
+            self._chk(self.lib.gsx_score_stats_edges(self.h, C.byref(sp)), "gsx_score_stats_edges")
+        else:
+            ed = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+            sp.n_edges = len(ed)
+            for k, x in enumerate(ed[: abi.GSX_SS_MAX_EDGES]):
+                sp.edges[k] = x
+        if out_ptrs is not None:
+            out = abi.ScorePartsOut(*[self._p(p).value if p is not None else None for p in out_ptrs])
+            self._chk(self.lib.gsx_score_parts(self.h, C.byref(sp), C.byref(out)), "gsx_score_parts")
+            return None
+        B = min(sp.n_edges, abi.GSX_SS_MAX_EDGES) + 1
+        n, E, NC = self.n_nodes, self.n_pairs, abi.GSX_CAUSES
+        parts = np.zeros((E, abi.GSX_PARTS), dtype=np.float64) if per_pair else None
+        cause = np.full(E, abi.GSX_CAUSE_NONE, dtype=np.uint8) if per_pair else None
+        worst = np.full(E, abi.GSX_TOPIC_NONE, dtype=np.uint8) if per_pair else None
+        ch = np.zeros((B, NC), dtype=np.uint64)
+        th = np.zeros((B, self.n_topics + 1), dtype=np.uint64)
+        oc = np.zeros((n, NC), dtype=np.uint32) if per_node else None
+        pe = np.zeros((n, NC), dtype=np.uint32) if per_node else None
+        out = abi.ScorePartsOut(*[a.ctypes.data if a is not None and a.size else None
+                                  for a in (parts, cause, worst, ch, th, oc, pe)])
+        self._chk(self.lib.gsx_score_parts(self.h, C.byref(sp), C.byref(out)), "gsx_score_parts")
+        return ScoreParts(np.array(sp.edges[: B - 1], dtype=np.float64), ch, th, oc, pe, parts, cause, worst)
 
     def pending_credits(self, first_ptr: int, dup_ptr: int):
         """Copy the pending (GSX_CREDIT_DEFER) counts to caller memory (host or device pointers)."""

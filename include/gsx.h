@@ -390,6 +390,79 @@ int gsx_score_stats_edges(gsx_engine* e, gsx_score_stats_spec* spec);
  * zeros and +inf; all outputs NULL returns at once. */
 int gsx_score_stats(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_score_stats_out* out);
 
+/* ---- what each score is made of, reduced on the device ----------------------- */
+/* gsx_score_stats says how many pairs are below each threshold; this says why:
+ * per pair the weighted terms score() (score.go:258-335) adds up, which of
+ * P1 .. P7 is the lowest negative one (the pair's cause), on which topic the
+ * weighted topic score is lowest (its worst topic), and the selected pairs
+ * counted per (score bin, cause), per (score bin, worst topic), per (observer
+ * row, cause) and per (peer, cause), without a record leaving the device.
+ *
+ * The parts of a pair.  Every part starts at +0.0 and accumulates in ascending
+ * topic index over the scored topics; the operations are those written here,
+ * each rounded on its own (no fused multiply-add), on the record as score()
+ * reads it (counters with their pending decays, meshTime as of the last
+ * refresh): */
+#define GSX_PART_P1 0     /* sum of (p1 * w1) * topic_weight; only in-mesh records add                */
+#define GSX_PART_P2 1     /* ... (fmd * w2) * topic_weight                                             */
+#define GSX_PART_P3 2     /* ... (deficit^2 * w3) * topic_weight; only ACTIVE records with mmd < threshold add */
+#define GSX_PART_P3B 3    /* ... (mfp * w3b) * topic_weight                                            */
+#define GSX_PART_P4 4     /* ... ((imd * imd) * w4) * topic_weight                                     */
+#define GSX_PART_P5 5     /* app * AppSpecificWeight (always formed: inf * 0 is its NaN)               */
+#define GSX_PART_P6 6     /* w6 != 0 ? p6 * w6 : +0.0                                                  */
+#define GSX_PART_P7 7     /* bp > threshold ? excess^2 * w7 : +0.0                                     */
+#define GSX_PART_TOPICS 8 /* the topic sum exactly as score() holds it after the TopicScoreCap (:264-317) */
+#define GSX_PART_SCORE 9  /* score() itself: TOPICS, then + P5, + P6 (w6 != 0), + P7 (bp > threshold)  */
+#define GSX_PARTS 10
+#define GSX_CAUSE_NONE 8
+#define GSX_CAUSES 9
+#define GSX_TOPIC_NONE 0xFFu
+/* Parts 0-4 are the terms before the cap, each summed over the topics on its
+ * own: score() sums them topic by topic and then caps, so they do NOT add up
+ * bit for bit to TOPICS (and under a TopicScoreCap that bites, not at all).
+ * SCORE is bit for bit what gsx_scores returns for the pair (a NaN only has to
+ * be a NaN).  A pair without GSX_PAIR_PRESENT has every part +0.0, cause
+ * GSX_CAUSE_NONE and topic GSX_TOPIC_NONE.
+ *
+ * cause(p): the lowest j in 0 .. 7 whose part is < 0 and not above any other
+ * of parts 0 .. 7, with the comparisons as written: a NaN part is below
+ * nothing and above nothing, so it is never the cause and never hides one;
+ * GSX_CAUSE_NONE if no part is negative.
+ * topic(p): the lowest scored t whose weighted topic score (what score() adds
+ * for the topic, :311) is < 0 and not above any other topic's; GSX_TOPIC_NONE
+ * if none is negative.
+ *
+ * Selection and bins are gsx_score_stats's, from the same gsx_score_stats_spec
+ * (select, topic, edges; gsx_score_stats_edges fills the default edges): the
+ * bin of a pair is bin(SCORE), so a NaN score lands in the top bin, and each
+ * row of cause_hist and of topic_hist sums to gsx_score_stats's hist entry for
+ * the same spec. */
+typedef struct gsx_score_parts_out { /* every pointer: NULL (skipped), host or device memory */
+    double* pair_parts;   /* [n_pairs][GSX_PARTS]          every pair, selected or not */
+    uint8_t* pair_cause;  /* [n_pairs]                                                 */
+    uint8_t* pair_topic;  /* [n_pairs]                                                 */
+    uint64_t* cause_hist; /* [n_edges + 1][GSX_CAUSES]     selected pairs per score bin and cause */
+    uint64_t* topic_hist; /* [n_edges + 1][n_topics + 1]   ... per score bin and worst topic; last column: none */
+    uint32_t* obs_cause;  /* [n_nodes][GSX_CAUSES]         row u's selected peers per cause */
+    uint32_t* peer_cause; /* [n_nodes][GSX_CAUSES]         selected pairs with col[p] == v per cause */
+} gsx_score_parts_out;
+/* Settles exactly what gsx_scores settles first (deferred folds, queued
+ * events, stale pairs), reads the records as score() does (the pending decays
+ * of the deferred write-back applied in registers, nothing stored) and changes
+ * nothing a later call can observe.  Outputs are overwritten.  Device outputs
+ * are written in stream order with no host synchronisation; host outputs are
+ * complete on return (the tables through buffers the engine keeps, the pair
+ * outputs through buffers of the call: nothing else is of the size of the pair
+ * set).  All counting is integer adds, no floating-point atomics: bit-identical
+ * from run to run.  Floating-point sums of the parts over pairs are not
+ * offered: they would depend on the order.  Inside a gsx_timing_begin region
+ * the call's device work counts as one timed launch.
+ * GSX_EINVAL: as gsx_score_stats, and on a range shard (gsx_load_overlay_shard).
+ * GSX_ESTATE: no overlay loaded, or a sharded gossip exchange in flight.  All
+ * outputs NULL returns at once; an engine of no pairs writes nothing but
+ * zeroed tables. */
+int gsx_score_parts(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_score_parts_out* out);
+
 /* A consistency check of the engine's zero map (per 64-pair tile,
  * topic and penalty counter, "every present pair holds +0.0", which lets the
  * refresh pass skip the counter's load): *n = the entries that say zero while
