@@ -564,6 +564,55 @@ struct ScorePartsArgs {
     uint32_t* peer_cause;            // [n_total][SP_CAUSES]
 };
 hipError_t launch_score_parts(const DevState& s, const KernParams& kp, const ScorePartsArgs& a, hipStream_t st);
+// gsx_mesh_stats (gsx_mesh_stats.hip): the shape of the mesh.  A mesh link
+// (p, t): pair p present and connected, REC_IN_MESH on t.  Pass 1 (pairs)
+// counts the links and what they are (outbound, one-sided, negative, active,
+// by age bin, by class pair), the backoff entries and the fanout links into
+// tot / age_hist / class_links, and the degrees per (topic, node) into the
+// node tables; pass 2 (units) bins the node tables into the histograms and the
+// verdict columns of tot.  Any output may be null; everything is added to (the
+// caller zeroes it).  Pass 2 reads node_deg / node_out / node_in / node_honest
+// / fan_any, so the caller passes scratch where the user gave no table.
+constexpr uint32_t MS_COLS = 16, MS_MAX_AGE_EDGES = 8, MS_MAX_CLASSES = 8, MS_MAX_BINS = 64;  // GSX_MS_*
+enum {
+    MS_UNITS = 0, MS_EMPTY, MS_BELOW_DLO, MS_ABOVE_DHI, MS_BELOW_DOUT, MS_LINKS, MS_OUTBOUND, MS_ONE_SIDED,
+    MS_NEGATIVE, MS_ACTIVE, MS_FANOUT_UNITS, MS_FANOUT_LINKS, MS_BACKOFF, MS_BACKOFF_EXPIRED, MS_ECLIPSED,
+    MS_BELOW_HONEST
+};
+struct MeshStatsArgs {
+    const uint8_t* pflags;
+    const uint8_t* eflags;
+    const uint8_t* rflags;     // tiled record flags
+    const double* rec;         // tiled records (the GRAFT slot: age_hist only)
+    const double* score;       // null: NEGATIVE is not counted
+    const uint32_t* pair_obs;
+    const int32_t* col;
+    const uint32_t* rev;       // null: no reverse-pair test (ONE_SIDED stays 0)
+    const uint8_t* bo8;        // [topic / 8][pair] presence bits (null: no backoff counts)
+    const int64_t* backoff;    // [topic][pair] expiry, read where a bit is set
+    const uint64_t* fanout;    // [pair] topic bits (null: membership never set)
+    const uint64_t* sub;       // [node] joined topics (null: every node joined every topic)
+    const uint8_t* node_class; // [node] (null: no classes)
+    uint64_t n_pairs;
+    uint32_t n_topics, n_nodes, n_bins, n_age_edges, n_classes, hostile_mask, min_honest;
+    int32_t d_lo, d_hi, d_out;
+    int64_t now;
+    int64_t age_edges[MS_MAX_AGE_EDGES];
+    unsigned long long* tot;          // [T][MS_COLS]
+    unsigned long long* deg_hist;     // [T][n_bins]
+    unsigned long long* out_hist;     // [T][n_bins]
+    unsigned long long* in_hist;      // [T][n_bins]
+    unsigned long long* age_hist;     // [T][n_age_edges + 1]
+    unsigned long long* class_links;  // [T][C][C]
+    uint32_t* node_deg;               // [T][n_nodes]
+    uint32_t* node_out;               // [T][n_nodes]
+    uint32_t* node_in;                // [T][n_nodes]
+    uint32_t* node_class_deg;         // [T][n_nodes][C]
+    uint32_t* node_honest;            // [T][n_nodes]: mesh peers of a class that is not hostile (scratch)
+    unsigned long long* fan_any;      // [n_nodes]: topics with a fanout link in the node's row (scratch)
+};
+hipError_t launch_mesh_pairs(const MeshStatsArgs& a, hipStream_t st);
+hipError_t launch_mesh_units(const MeshStatsArgs& a, hipStream_t st);
 // The peer gater (gsx_gater.hip; peer_gater.go).  Per observer: validate,
 // throttle, last_throttle and the `hot` byte of the last gsx_accept_from (quiet
 // period, throttle and ratio all say "gate on").  Per group g (an (observer, IP)

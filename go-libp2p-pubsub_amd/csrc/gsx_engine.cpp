@@ -446,6 +446,17 @@ struct gsx_engine {
         // gsx_score_parts: the same for its four tables (the pair outputs are staged per call)
         unsigned long long *sp_cause_hist = nullptr, *sp_topic_hist = nullptr;
         uint32_t *sp_obs_cause = nullptr, *sp_peer_cause = nullptr;
+        // gsx_mesh_stats: the small tables in one block, the four [topic][node] tables
+        // (degree, outbound, in-degree, honest degree: the user's where given, else
+        // these, which pass 2 reads), the class degrees, the fanout words and the
+        // classes of a host array; each sized once for the overlay, kept across calls
+        unsigned long long* ms_tab = nullptr;
+        uint32_t* ms_node[4] = {nullptr, nullptr, nullptr, nullptr};
+        uint32_t* ms_ncd = nullptr;
+        unsigned long long* ms_fan = nullptr;
+        uint8_t* ms_class = nullptr;
+        std::vector<uint8_t> ms_hclass;  // (host staging of the classes, alive until their upload is done)
+        bool ms_class_busy = false;
     } prop;
     bool prop_track = true;  // gsx_prop_set_tracking: keep first-deliverer rows (gsx_prop_results)
 
@@ -1111,7 +1122,9 @@ void free_state(gsx_engine* e) {
                   e->prop.tr_sset, e->prop.tr_planes, e->prop.tr_msg, e->prop.tr_node, e->prop.tr_pair,
                   e->prop.tr_nbytes, e->prop.tr_pbytes,
                   e->prop.ss_hist, e->prop.ss_obs_bins, e->prop.ss_peer_bins, e->prop.ss_obs_min, e->prop.ss_peer_min,
-                  e->prop.sp_cause_hist, e->prop.sp_topic_hist, e->prop.sp_obs_cause, e->prop.sp_peer_cause};
+                  e->prop.sp_cause_hist, e->prop.sp_topic_hist, e->prop.sp_obs_cause, e->prop.sp_peer_cause,
+                  e->prop.ms_tab, e->prop.ms_node[0], e->prop.ms_node[1], e->prop.ms_node[2], e->prop.ms_node[3],
+                  e->prop.ms_ncd, e->prop.ms_fan, e->prop.ms_class};
     for (void* p : pp)
         if (p) (void)hipFree(p);
     std::vector<hipEvent_t> evs = std::move(e->prop.ev);
@@ -5017,6 +5030,185 @@ int gsx_score_parts(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_s
     if (rc && (t_pp || t_pc || t_pt)) (void)hipStreamSynchronize(e->stream);
     drop();
     return rc;
+}
+
+int gsx_mesh_stats(gsx_engine* e, const gsx_mesh_stats_spec* spec, const gsx_mesh_stats_out* out) {
+    static_assert(gsx::MS_COLS == GSX_MS_COLS && gsx::MS_MAX_AGE_EDGES == GSX_MS_MAX_AGE_EDGES &&
+                      gsx::MS_MAX_CLASSES == GSX_MS_MAX_CLASSES && gsx::MS_MAX_BINS == GSX_MS_MAX_BINS &&
+                      gsx::MS_UNITS == GSX_MS_UNITS && gsx::MS_EMPTY == GSX_MS_EMPTY &&
+                      gsx::MS_BELOW_DLO == GSX_MS_BELOW_DLO && gsx::MS_ABOVE_DHI == GSX_MS_ABOVE_DHI &&
+                      gsx::MS_BELOW_DOUT == GSX_MS_BELOW_DOUT && gsx::MS_LINKS == GSX_MS_LINKS &&
+                      gsx::MS_OUTBOUND == GSX_MS_OUTBOUND && gsx::MS_ONE_SIDED == GSX_MS_ONE_SIDED &&
+                      gsx::MS_NEGATIVE == GSX_MS_NEGATIVE && gsx::MS_ACTIVE == GSX_MS_ACTIVE &&
+                      gsx::MS_FANOUT_UNITS == GSX_MS_FANOUT_UNITS && gsx::MS_FANOUT_LINKS == GSX_MS_FANOUT_LINKS &&
+                      gsx::MS_BACKOFF == GSX_MS_BACKOFF && gsx::MS_BACKOFF_EXPIRED == GSX_MS_BACKOFF_EXPIRED &&
+                      gsx::MS_ECLIPSED == GSX_MS_ECLIPSED && gsx::MS_BELOW_HONEST == GSX_MS_BELOW_HONEST,
+                  "the kernel's constants are the header's");
+    if (!e || !spec || !out) return GSX_EINVAL;
+    if (spec->n_bins < 2 || spec->n_bins > GSX_MS_MAX_BINS) return fail(e, GSX_EINVAL, "2 <= n_bins <= GSX_MS_MAX_BINS");
+    if (spec->n_age_edges > GSX_MS_MAX_AGE_EDGES) return fail(e, GSX_EINVAL, "more than GSX_MS_MAX_AGE_EDGES edges");
+    for (uint32_t k = 1; k < spec->n_age_edges; ++k)
+        if (!(spec->age_edges_ns[k] > spec->age_edges_ns[k - 1]))
+            return fail(e, GSX_EINVAL, "age edges must be strictly ascending");
+    if (spec->node_class && (spec->n_classes == 0 || spec->n_classes > GSX_MS_MAX_CLASSES))
+        return fail(e, GSX_EINVAL, "1 <= n_classes <= GSX_MS_MAX_CLASSES with node_class");
+    if (!spec->node_class && (out->class_links || out->node_class_deg))
+        return fail(e, GSX_EINVAL, "class_links / node_class_deg need node_class");
+    if (int rc = gx_busy(e)) return rc;  // (before the shard test: only a range shard can have one in flight)
+    if (e->sharded()) return fail(e, GSX_EINVAL, "gsx_mesh_stats is not offered on a range shard");
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    void* const user[10] = {out->topic_tot, out->deg_hist, out->out_hist,  out->in_hist,  out->age_hist,
+                            out->class_links, out->node_deg, out->node_out, out->node_in, out->node_class_deg};
+    if (std::all_of(user, user + 10, [](void* p) { return p == nullptr; })) return GSX_OK;
+    if (e->n_nodes == 0) return GSX_OK;
+    auto& P = e->prop;
+    const size_t N = e->n_nodes, T = e->T, E = e->E, TN = T * N;
+    const uint32_t C = spec->node_class ? spec->n_classes : 0;
+    // the classes, checked on the host before any launch; a host array goes to the engine's copy
+    const uint8_t* d_class = nullptr;
+    if (spec->node_class) {
+        if (P.ms_class_busy) HIPCHK(e, hipStreamSynchronize(e->stream));  // (the last upload may still read the staging)
+        P.ms_class_busy = false;
+        const bool dev = on_device(spec->node_class);
+        if (dev) {
+            P.ms_hclass.resize(N);
+            HIPCHK(e, hipMemcpyAsync(P.ms_hclass.data(), spec->node_class, N, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(e, hipStreamSynchronize(e->stream));
+        } else {
+            P.ms_hclass.assign(spec->node_class, spec->node_class + N);
+        }
+        for (uint8_t c : P.ms_hclass)
+            if (c >= C) return fail(e, GSX_EINVAL, "a node's class >= n_classes");
+        if (dev) {
+            d_class = spec->node_class;
+        } else {
+            if (!P.ms_class)
+                if (int rc = dalloc(e, &P.ms_class, N)) return rc;
+            HIPCHK(e, hipMemcpyAsync(P.ms_class, P.ms_hclass.data(), N, hipMemcpyHostToDevice, e->stream));
+            P.ms_class_busy = true;
+            d_class = P.ms_class;
+        }
+    }
+    // NEGATIVE reads the score vector as gsx_score_stats does; the other columns the settled flags
+    if (E) {
+        if (out->topic_tot) {
+            if (int rc = ensure_scores(e)) return rc;
+        } else {
+            if (int rc = fold_deferred(e)) return rc;
+            if (int rc = flush(e)) return rc;
+        }
+    }
+    // sizes (elements) of the ten outputs; the first six are u64 tables, the others u32 node tables
+    const size_t nb = spec->n_bins, nab = (size_t)spec->n_age_edges + 1;
+    const size_t len[10] = {T * GSX_MS_COLS, T * nb, T * nb, T * nb, T * nab, T * C * C, TN, TN, TN, TN * C};
+    constexpr size_t MAXT = GSX_MAX_TOPICS;
+    const size_t tab_off[7] = {0,
+                               MAXT * GSX_MS_COLS,
+                               MAXT * (GSX_MS_COLS + GSX_MS_MAX_BINS),
+                               MAXT * (GSX_MS_COLS + 2 * GSX_MS_MAX_BINS),
+                               MAXT * (GSX_MS_COLS + 3 * GSX_MS_MAX_BINS),
+                               MAXT * (GSX_MS_COLS + 3 * GSX_MS_MAX_BINS + GSX_MS_MAX_AGE_EDGES + 1),
+                               MAXT * (GSX_MS_COLS + 3 * GSX_MS_MAX_BINS + GSX_MS_MAX_AGE_EDGES + 1 +
+                                       GSX_MS_MAX_CLASSES * GSX_MS_MAX_CLASSES)};
+    // device memory is written in place, in stream order; host memory gets a copy of the engine's buffers
+    bool host[10];
+    void* dev[10];
+    for (int k = 0; k < 10; ++k) {
+        host[k] = user[k] && len[k] && !on_device(user[k]);
+        dev[k] = host[k] || !len[k] ? nullptr : user[k];
+    }
+    const bool units = out->topic_tot || out->deg_hist || out->out_hist || out->in_hist;  // pass 2 runs
+    // what pass 2 reads where the user gave no (device) table: degree, outbound, in-degree, honest degree
+    const bool need[4] = {out->topic_tot || out->deg_hist || host[6], out->topic_tot || out->out_hist || host[7],
+                          out->in_hist || host[8], out->topic_tot && d_class};
+    if (std::any_of(host, host + 6, [](bool b) { return b; }) && !P.ms_tab)
+        if (int rc = dalloc(e, &P.ms_tab, tab_off[6])) return rc;
+    for (int k = 0; k < 6; ++k)
+        if (host[k]) dev[k] = P.ms_tab + tab_off[k];
+    uint32_t* node[4] = {static_cast<uint32_t*>(dev[6]), static_cast<uint32_t*>(dev[7]), static_cast<uint32_t*>(dev[8]),
+                         nullptr};
+    for (int k = 0; k < 4; ++k)
+        if (!node[k] && need[k]) {
+            if (!P.ms_node[k])
+                if (int rc = dalloc(e, &P.ms_node[k], TN)) return rc;
+            node[k] = P.ms_node[k];
+        }
+    if (host[9]) {
+        if (!P.ms_ncd)
+            if (int rc = dalloc(e, &P.ms_ncd, TN * GSX_MS_MAX_CLASSES)) return rc;
+        dev[9] = P.ms_ncd;
+    }
+    const bool fan = out->topic_tot && e->members_on;
+    if (fan && !P.ms_fan)
+        if (int rc = dalloc(e, &P.ms_fan, N)) return rc;
+
+    using u64p = unsigned long long*;
+    gsx::MeshStatsArgs a{};
+    a.pflags = e->d_pflags;
+    a.eflags = e->d_eflags;
+    a.rflags = e->d_rflags;
+    a.rec = e->d_rec;
+    a.score = out->topic_tot ? e->d_score : nullptr;
+    a.pair_obs = e->d_pair_obs;
+    a.col = e->d_col;
+    a.rev = spec->symmetry && out->topic_tot ? e->d_rev : nullptr;
+    a.bo8 = out->topic_tot ? e->d_bo8 : nullptr;
+    a.backoff = e->d_backoff;
+    a.fanout = fan ? e->d_fanout : nullptr;
+    a.sub = e->members_on ? e->d_sub : nullptr;
+    a.node_class = d_class;
+    a.n_pairs = E;
+    a.n_topics = (uint32_t)T;
+    a.n_nodes = (uint32_t)N;
+    a.n_bins = spec->n_bins;
+    a.n_age_edges = spec->n_age_edges;
+    a.n_classes = C;
+    a.hostile_mask = spec->hostile_mask;
+    a.min_honest = spec->min_honest;
+    a.d_lo = e->gp.d_lo;
+    a.d_hi = e->gp.d_hi;
+    a.d_out = e->gp.d_out;
+    a.now = spec->now_ns;
+    for (uint32_t k = 0; k < spec->n_age_edges; ++k) a.age_edges[k] = spec->age_edges_ns[k];
+    a.tot = static_cast<u64p>(dev[0]);
+    a.deg_hist = static_cast<u64p>(dev[1]);
+    a.out_hist = static_cast<u64p>(dev[2]);
+    a.in_hist = static_cast<u64p>(dev[3]);
+    a.age_hist = static_cast<u64p>(dev[4]);
+    a.class_links = static_cast<u64p>(dev[5]);
+    a.node_deg = node[0];
+    a.node_out = node[1];
+    a.node_in = node[2];
+    a.node_honest = node[3];
+    a.node_class_deg = static_cast<uint32_t*>(dev[9]);
+    a.fan_any = fan ? P.ms_fan : nullptr;
+
+    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
+    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    for (int k = 0; k < 6; ++k)
+        if (dev[k]) HIPCHK(e, hipMemsetAsync(dev[k], 0, 8 * len[k], e->stream));
+    for (int k = 0; k < 4; ++k)
+        if (node[k]) HIPCHK(e, hipMemsetAsync(node[k], 0, 4 * TN, e->stream));
+    if (dev[9]) HIPCHK(e, hipMemsetAsync(dev[9], 0, 4 * len[9], e->stream));
+    if (a.fan_any) HIPCHK(e, hipMemsetAsync(a.fan_any, 0, 8 * N, e->stream));
+    HIPCHK(e, gsx::launch_mesh_pairs(a, e->stream));
+    if (units) HIPCHK(e, gsx::launch_mesh_units(a, e->stream));
+    if (region) {
+        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
+        ++e->t_used;
+    }
+    bool any_host = false;
+    for (int k = 0; k < 10; ++k) {
+        if (!host[k]) continue;
+        const void* src = k < 6 ? dev[k] : k < 9 ? static_cast<void*>(node[k - 6]) : dev[9];
+        HIPCHK(e, hipMemcpyAsync(user[k], src, (k < 6 ? 8 : 4) * len[k], hipMemcpyDeviceToHost, e->stream));
+        any_host = true;
+    }
+    if (any_host) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));
+        P.ms_class_busy = false;
+    }
+    return GSX_OK;
 }
 
 // ---- the peer gater (peer_gater.go) and AcceptFrom (gossipsub.go:583-594) ------

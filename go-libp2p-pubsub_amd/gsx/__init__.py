@@ -5,4 +5,4 @@ The engine is the HIP library built from ../csrc; this package only loads it
 """
 from . import abi  # noqa: F401
 from .abi import GsxError, load_library  # noqa: F401
-from .engine import ConnTrim, Engine, PropStats, PropTraffic, ScoreParts, ScoreStats, TimedStats, TimedTraffic, make_struct  # noqa: F401
+from .engine import ConnTrim, Engine, MeshStats, PropStats, PropTraffic, ScoreParts, ScoreStats, TimedStats, TimedTraffic, make_struct  # noqa: F401

@@ -462,6 +462,44 @@ class ScorePartsOut(C.Structure):
     ]
 
 
+# gsx_mesh_stats: GSX_MS_* (the columns of topic_tot, in order)
+MS_COL_NAMES = ("units", "empty", "below_dlo", "above_dhi", "below_dout", "links", "outbound", "one_sided", "negative",
+                "active", "fanout_units", "fanout_links", "backoff", "backoff_expired", "eclipsed", "below_honest")
+(GSX_MS_UNITS, GSX_MS_EMPTY, GSX_MS_BELOW_DLO, GSX_MS_ABOVE_DHI, GSX_MS_BELOW_DOUT, GSX_MS_LINKS, GSX_MS_OUTBOUND,
+ GSX_MS_ONE_SIDED, GSX_MS_NEGATIVE, GSX_MS_ACTIVE, GSX_MS_FANOUT_UNITS, GSX_MS_FANOUT_LINKS, GSX_MS_BACKOFF,
+ GSX_MS_BACKOFF_EXPIRED, GSX_MS_ECLIPSED, GSX_MS_BELOW_HONEST) = range(16)
+GSX_MS_COLS = 16
+GSX_MS_MAX_AGE_EDGES = 8
+GSX_MS_MAX_CLASSES = 8
+GSX_MS_MAX_BINS = 64
+
+
+class MeshStatsSpec(C.Structure):
+    """gsx_mesh_stats_spec"""
+
+    _fields_ = [
+        ("now_ns", C.c_int64),
+        ("n_bins", C.c_uint32),
+        ("n_age_edges", C.c_uint32),
+        ("age_edges_ns", C.c_int64 * GSX_MS_MAX_AGE_EDGES),
+        ("node_class", C.c_void_p),
+        ("n_classes", C.c_uint32),
+        ("hostile_mask", C.c_uint32),
+        ("min_honest", C.c_uint32),
+        ("symmetry", C.c_uint32),
+    ]
+
+
+MS_OUT_FIELDS = ("topic_tot", "deg_hist", "out_hist", "in_hist", "age_hist", "class_links", "node_deg", "node_out",
+                 "node_in", "node_class_deg")
+
+
+class MeshStatsOut(C.Structure):
+    """gsx_mesh_stats_out: host or device addresses, None skips an output"""
+
+    _fields_ = [(f, C.c_void_p) for f in MS_OUT_FIELDS]
+
+
 # the peer gater (peer_gater.go) and AcceptFrom
 GSX_ACCEPT_NONE = 0
 GSX_ACCEPT_CONTROL = 1
@@ -658,6 +696,7 @@ SIGNATURES = {
     "gsx_score_stats_edges": (C.c_int, [C.c_void_p, P(ScoreStatsSpec)]),
     "gsx_score_stats": (C.c_int, [C.c_void_p, P(ScoreStatsSpec), P(ScoreStatsOut)]),
     "gsx_score_parts": (C.c_int, [C.c_void_p, P(ScoreStatsSpec), P(ScorePartsOut)]),
+    "gsx_mesh_stats": (C.c_int, [C.c_void_p, P(MeshStatsSpec), P(MeshStatsOut)]),
     "gsx_prop_set_tracking": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_prop_duplicates": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_size_t]),
     # (msg_bytes: host; the outputs host or device pointers, like gsx_prop_stats: passed as addresses)

@@ -510,6 +510,84 @@ class ScoreParts:
         return np.nonzero(self.peer_cause[:, self._cause(cause)])[0]
 
 
+class MeshStats:
+    """The shape of the mesh (gsx_mesh_stats): topic_tot [T, 16] u64 (columns abi.MS_COL_NAMES),
+    deg_hist / out_hist / in_hist [T, n_bins] u64 (units by degree, outbound degree, in-degree;
+    the last bin: >= n_bins - 1), age_hist [T, len(age_edges) + 1] u64 and class_links [T, C, C]
+    u64 (mesh links by age bin, by (observer class, peer class)), node_deg / node_out / node_in
+    [T, n] u32 and node_class_deg [T, n, C] u32.  Any of them may be None.  Everything below is
+    numpy on those tables."""
+
+    def __init__(self, n_topics, n_bins, age_edges_ns=(), n_classes=0, topic_tot=None, deg_hist=None, out_hist=None,
+                 in_hist=None, age_hist=None, class_links=None, node_deg=None, node_out=None, node_in=None,
+                 node_class_deg=None):
+        self.n_topics, self.n_bins, self.n_classes = int(n_topics), int(n_bins), int(n_classes)
+        self.age_edges_ns = np.ascontiguousarray(age_edges_ns, dtype=np.int64).reshape(-1)
+        T, B, NC = self.n_topics, self.n_bins, self.n_classes
+
+        def arr(a, dtype, *shape):
+            return None if a is None else np.ascontiguousarray(a, dtype=dtype).reshape(*shape)
+
+        self.topic_tot = arr(topic_tot, np.uint64, T, abi.GSX_MS_COLS)
+        self.deg_hist = arr(deg_hist, np.uint64, T, B)
+        self.out_hist = arr(out_hist, np.uint64, T, B)
+        self.in_hist = arr(in_hist, np.uint64, T, B)
+        self.age_hist = arr(age_hist, np.uint64, T, len(self.age_edges_ns) + 1)
+        self.class_links = arr(class_links, np.uint64, T, NC, NC)
+        self.node_deg = arr(node_deg, np.uint32, T, -1)
+        self.node_out = arr(node_out, np.uint32, T, -1)
+        self.node_in = arr(node_in, np.uint32, T, -1)
+        self.node_class_deg = arr(node_class_deg, np.uint32, T, -1, NC) if NC else None
+
+    @staticmethod
+    def _col(col) -> int:
+        return abi.MS_COL_NAMES.index(col) if isinstance(col, str) else int(col)
+
+    def total(self, col, topic=None) -> int:
+        """Column `col` (a name of abi.MS_COL_NAMES or GSX_MS_*) of one topic, or summed over the topics."""
+        c = self.topic_tot[:, self._col(col)]
+        return int(c.sum()) if topic is None else int(c[topic])
+
+    def degree(self, t: int) -> np.ndarray:
+        """[n] u32: the mesh degree of every node on topic t."""
+        return self.node_deg[t]
+
+    def outbound(self, t: int) -> np.ndarray:
+        """[n] u32: the outbound mesh peers of every node on topic t."""
+        return self.node_out[t]
+
+    def indegree(self, t: int) -> np.ndarray:
+        """[n] u32: the mesh links on topic t that point at each node."""
+        return self.node_in[t]
+
+    def _ratio(self, num, den, t):
+        d = self.total(den, t)
+        return sum(self.total(c, t) for c in num) / d if d else float("nan")
+
+    def within_bounds(self, t: int) -> float:
+        """The units of topic t with Dlo <= degree <= Dhi, over its units; nan without units."""
+        d = self.total("units", t)
+        return 1.0 - (self.total("below_dlo", t) + self.total("above_dhi", t)) / d if d else float("nan")
+
+    def one_sided_ratio(self, t=None) -> float:
+        """One-sided mesh links over mesh links (topic t, or all topics); nan without links."""
+        return self._ratio(("one_sided",), "links", t)
+
+    def eclipsed(self, t=None) -> int:
+        return self.total("eclipsed", t)
+
+    def below_honest(self, t=None) -> int:
+        return self.total("below_honest", t)
+
+    def class_share(self, t: int) -> np.ndarray:
+        """[C, C] f64: row c = where the mesh links of class-c observers point, as shares of the row
+        (nan for a class without mesh links)."""
+        m = self.class_links[t].astype(np.float64)
+        s = m.sum(1, keepdims=True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(s > 0, m / np.maximum(s, 1), np.nan)
+
+
 class ConnTrim:
     """A forced trim of every observer's connections (gsx_conn_trim): trim[p] = 1
     for the pairs it closes, node_trimmed[u] their number in u's row;
@@ -1263,6 +1341,53 @@ class Engine:
                                   for a in (parts, cause, worst, ch, th, oc, pe)])
         self._chk(self.lib.gsx_score_parts(self.h, C.byref(sp), C.byref(out)), "gsx_score_parts")
         return ScoreParts(np.array(sp.edges[: B - 1], dtype=np.float64), ch, th, oc, pe, parts, cause, worst)
+
+    def mesh_stats(self, now_ns: int, n_bins: int = 33, age_edges_ns=(), node_class=None, n_classes: int = 0,
+                   hostile_mask: int = 0, min_honest: int = 0, per_node: bool = True, symmetry: bool = True,
+                   out_ptrs=None):
+        """gsx_mesh_stats -> MeshStats: per topic the mesh links and what they are, the backoff
+        entries and the fanout, the units per degree bin and per heartbeat verdict; with per_node
+        the degree, outbound degree and in-degree of every (topic, node); with node_class ([n] u8,
+        an array or a device tensor, values < n_classes, hostile_mask bit c: class c is hostile) the
+        links per class pair, the class degrees and the eclipsed / below-min_honest units.
+
+        out_ptrs = abi.MS_OUT_FIELDS in order: device pointers or tensors (None / 0 skips one)
+        written in stream order with no host sync, as score_stats takes them; then -> None."""
+        ed = np.ascontiguousarray(age_edges_ns, dtype=np.int64).reshape(-1)
+        sp = abi.MeshStatsSpec(now_ns=int(now_ns), n_bins=int(n_bins), n_age_edges=len(ed), n_classes=int(n_classes),
+                               hostile_mask=int(hostile_mask), min_honest=int(min_honest), symmetry=int(bool(symmetry)))
+        for k, x in enumerate(ed[: abi.GSX_MS_MAX_AGE_EDGES]):
+            sp.age_edges_ns[k] = int(x)
+        keep = None
+        if node_class is not None:
+            if hasattr(node_class, "data_ptr"):
+                sp.node_class = node_class.data_ptr()
+            else:
+                keep = np.ascontiguousarray(node_class, dtype=np.uint8).reshape(-1)
+                if len(keep) != self.n_nodes:
+                    raise ValueError("node_class: one class per node")
+                sp.node_class = keep.ctypes.data if len(keep) else None
+        if out_ptrs is not None:
+            out = abi.MeshStatsOut(*[self._p(p).value if p is not None else None for p in out_ptrs])
+            self._chk(self.lib.gsx_mesh_stats(self.h, C.byref(sp), C.byref(out)), "gsx_mesh_stats")
+            return None
+        T, n = self.n_topics, self.n_nodes
+        B = min(max(int(n_bins), 1), abi.GSX_MS_MAX_BINS)
+        A = min(len(ed), abi.GSX_MS_MAX_AGE_EDGES) + 1
+        NC = min(int(n_classes), abi.GSX_MS_MAX_CLASSES) if node_class is not None else 0
+        tabs = {"topic_tot": np.zeros((T, abi.GSX_MS_COLS), dtype=np.uint64),
+                "deg_hist": np.zeros((T, B), dtype=np.uint64), "out_hist": np.zeros((T, B), dtype=np.uint64),
+                "in_hist": np.zeros((T, B), dtype=np.uint64), "age_hist": np.zeros((T, A), dtype=np.uint64),
+                "class_links": np.zeros((T, NC, NC), dtype=np.uint64) if NC else None,
+                "node_deg": np.zeros((T, n), dtype=np.uint32) if per_node else None,
+                "node_out": np.zeros((T, n), dtype=np.uint32) if per_node else None,
+                "node_in": np.zeros((T, n), dtype=np.uint32) if per_node else None,
+                "node_class_deg": np.zeros((T, n, NC), dtype=np.uint32) if per_node and NC else None}
+        out = abi.MeshStatsOut(*[tabs[f].ctypes.data if tabs[f] is not None and tabs[f].size else None
+                                 for f in abi.MS_OUT_FIELDS])
+        self._chk(self.lib.gsx_mesh_stats(self.h, C.byref(sp), C.byref(out)), "gsx_mesh_stats")
+        del keep
+        return MeshStats(T, B, ed[: A - 1], NC, **tabs)
 
     def pending_credits(self, first_ptr: int, dup_ptr: int):
         """Copy the pending (GSX_CREDIT_DEFER) counts to caller memory (host or device pointers)."""

@@ -463,6 +463,91 @@ typedef struct gsx_score_parts_out { /* every pointer: NULL (skipped), host or d
  * zeroed tables. */
 int gsx_score_parts(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_score_parts_out* out);
 
+/* ---- the shape of the mesh, reduced on the device ----------------------------- */
+/* What the heartbeat builds: per topic the mesh links and what they are, the
+ * degrees of every node, and the units per degree and per heartbeat verdict
+ * (mesh sizes within [Dlo, Dhi], Dout outbound peers, honest peers kept against
+ * sybils: what the reference's router tests assert), without a record leaving
+ * the device.
+ *
+ * Mesh link (p, t): pair p = (u -> v) has GSX_PAIR_PRESENT and
+ * GSX_PAIR_CONNECTED and its record on t has GSX_REC_IN_MESH.
+ * Unit (u, t): node u has joined t (no subscriptions set: every node, every
+ * topic).  Degrees are counted for every node; the histograms and the verdict
+ * columns over units only.
+ * Columns of topic_tot, per topic: */
+#define GSX_MS_UNITS 0            /* units                                                        */
+#define GSX_MS_EMPTY 1            /* units of degree 0                                            */
+#define GSX_MS_BELOW_DLO 2        /* units of degree < Dlo                                        */
+#define GSX_MS_ABOVE_DHI 3        /* units of degree > Dhi                                        */
+#define GSX_MS_BELOW_DOUT 4       /* units of outbound degree < Dout                              */
+#define GSX_MS_LINKS 5            /* mesh links                                                   */
+#define GSX_MS_OUTBOUND 6         /* ... whose edge flag has GSX_EDGE_OUTBOUND                    */
+#define GSX_MS_ONE_SIDED 7        /* ... whose reverse pair (v -> u) does not exist, is not present and connected, or is no mesh link on t */
+#define GSX_MS_NEGATIVE 8         /* ... with score[p] < 0 (the score gsx_scores returns; a NaN is not below 0) */
+#define GSX_MS_ACTIVE 9           /* ... with GSX_REC_ACTIVE                                      */
+#define GSX_MS_FANOUT_UNITS 10    /* (u, t) with a pair of u's row in t's fanout                  */
+#define GSX_MS_FANOUT_LINKS 11    /* pairs whose fanout word has bit t                            */
+#define GSX_MS_BACKOFF 12         /* backoff entries (pair, t) with expiry > now_ns               */
+#define GSX_MS_BACKOFF_EXPIRED 13 /* backoff entries with expiry <= now_ns (not yet cleared)      */
+#define GSX_MS_ECLIPSED 14        /* units of a non-hostile node with degree >= 1 and no honest mesh peer */
+#define GSX_MS_BELOW_HONEST 15    /* units of a non-hostile node with fewer than min_honest honest mesh peers */
+#define GSX_MS_COLS 16
+#define GSX_MS_MAX_AGE_EDGES 8
+#define GSX_MS_MAX_CLASSES 8
+#define GSX_MS_MAX_BINS 64
+/* D, Dlo, Dhi, Dout are those of the last gsx_set_gossipsub_params (the
+ * defaults if none).  A backoff entry is one gsx_export_backoff shows as
+ * non-zero; the fanout columns are 0 while membership was never set.  The age
+ * of a link is now_ns - graftTime (wrapping int64), bin(age) = the number of k
+ * with !(age < age_edges_ns[k]): gsx_score_stats's rule.  Classes: node_class
+ * [n_nodes] u8 (host or device memory; a device array is copied to the host
+ * once per call to be checked), every value < n_classes; a mesh peer is honest
+ * when hostile_mask has no bit for its class; the two class verdicts, and
+ * class_links / node_class_deg, need node_class. */
+typedef struct gsx_mesh_stats_spec {
+    int64_t now_ns;
+    uint32_t n_bins;      /* 2 .. GSX_MS_MAX_BINS: degree d is in bin min(d, n_bins - 1)   */
+    uint32_t n_age_edges; /* 0 .. GSX_MS_MAX_AGE_EDGES                                     */
+    int64_t age_edges_ns[GSX_MS_MAX_AGE_EDGES]; /* strictly ascending                      */
+    const uint8_t* node_class; /* NULL: no classes                                          */
+    uint32_t n_classes;        /* 1 .. GSX_MS_MAX_CLASSES with node_class                   */
+    uint32_t hostile_mask;     /* bit c: class c is hostile                                 */
+    uint32_t min_honest;
+    uint32_t symmetry;         /* 0: no reverse-pair test, GSX_MS_ONE_SIDED stays 0         */
+} gsx_mesh_stats_spec;
+
+typedef struct gsx_mesh_stats_out { /* every pointer: NULL (skipped), host or device memory */
+    uint64_t* topic_tot;      /* [n_topics][GSX_MS_COLS]                                    */
+    uint64_t* deg_hist;       /* [n_topics][n_bins]          units by degree                */
+    uint64_t* out_hist;       /* [n_topics][n_bins]          units by outbound degree       */
+    uint64_t* in_hist;        /* [n_topics][n_bins]          units by in-degree             */
+    uint64_t* age_hist;       /* [n_topics][n_age_edges + 1] mesh links by age bin          */
+    uint64_t* class_links;    /* [n_topics][C][C]            mesh links by (class of u, class of v) */
+    uint32_t* node_deg;       /* [n_topics][n_nodes]         mesh links of row u on t       */
+    uint32_t* node_out;       /* [n_topics][n_nodes]         ... that are outbound          */
+    uint32_t* node_in;        /* [n_topics][n_nodes]         mesh links (p, t) with col[p] == v */
+    uint32_t* node_class_deg; /* [n_topics][n_nodes][C]      mesh peers of (u, t) per class */
+} gsx_mesh_stats_out;
+/* With topic_tot, settles exactly what gsx_scores settles first (deferred
+ * folds, queued events, stale pairs: GSX_MS_NEGATIVE reads the scores); without
+ * it only the deferred folds and queued events, which is all the flags depend
+ * on.  Changes nothing a later call can observe.  Outputs are overwritten.
+ * Device outputs are written in stream order with no host synchronisation,
+ * unless node_class is device memory: its check on the host is one copy of
+ * n_nodes bytes and one synchronisation per call (pass a host array to avoid
+ * it).  Host outputs are complete on return, through buffers the engine
+ * keeps: of the size of the node tables at most, never of the record set.  All counting is integer adds: bit-identical from run to run.  Inside a
+ * gsx_timing_begin region the call's device work counts as one timed launch.
+ * GSX_EINVAL: a NULL argument; n_bins outside 2 .. GSX_MS_MAX_BINS; more than
+ * GSX_MS_MAX_AGE_EDGES edges or edges not strictly ascending; node_class with
+ * n_classes 0 or > GSX_MS_MAX_CLASSES, or holding a value >= n_classes;
+ * class_links or node_class_deg without node_class; a range shard
+ * (gsx_load_overlay_shard: the reverse pair lives on another rank).
+ * GSX_ESTATE: no overlay loaded, or a sharded gossip exchange in flight.  All
+ * outputs NULL returns at once; an engine of no nodes writes nothing. */
+int gsx_mesh_stats(gsx_engine* e, const gsx_mesh_stats_spec* spec, const gsx_mesh_stats_out* out);
+
 /* A consistency check of the engine's zero map (per 64-pair tile,
  * topic and penalty counter, "every present pair holds +0.0", which lets the
  * refresh pass skip the counter's load): *n = the entries that say zero while
