@@ -22,8 +22,16 @@ struct DevTopicParams {
     double w3b, d3b;
     double w4, d4;
     int32_t scored;
-    int32_t pad;
+    // all four decays lie in (0, 1): pending decays may run as the multiply
+    // chain (decay_chain_ok, below; rec_decay, gsx_ops.h).  The host validates
+    // a decay only where its weight is not zero, so a scored topic can carry
+    // any value in the others: such a topic keeps the stepwise form.
+    int32_t chain;
 };
+
+// The precondition of the decay chain (gsx_ops.h) on one decay constant.  NaN
+// fails both compares.
+__host__ __device__ __forceinline__ bool decay_chain_ok(double d) { return d > 0.0 && d < 1.0; }
 
 // DevTopicParams::inv_q1 for a quantum: 1 / q1 rounded once, or 0 for a quantum
 // below zero (div_q1, gsx_ops.h, then always divides plainly).
@@ -53,7 +61,7 @@ struct KernParams {
 // Records (one per observer, peer, topic: the reference's topicStats,
 // score.go:37-62) are tiled by 64 pairs — one wavefront's lanes:
 //   rec   [p/64][t][field][64]  8-byte fields, field = FMD, MMD, MFP, IMD, GRAFT
-//   rflag [p/64][t][64]         u8: IN_MESH | ACTIVE | FRESH | write-back epoch (2 bits)
+//   rflag [p/64][t][64]         u8: IN_MESH | ACTIVE | FRESH | write-back epoch (4 bits)
 // so the lanes of a wave read each field of a topic as one contiguous 512-B
 // span and a wave's whole working set (T x 2.6 KB) is one contiguous block
 // of HBM.  meshTime is not stored: for an in-mesh record it is
@@ -110,7 +118,7 @@ struct DevState {
     uint8_t* rflags;      // tiled record flags
     uint8_t* zmap;        // per (tile, topic, MFP | IMD): ZM_ZERO / ZM_MAYBE
     uint8_t* pzmap;       // per (tile, PZ_APP | PZ_P6): ZM_ZERO / ZM_MAYBE
-    uint8_t* pflags;      // per pair: PRESENT | CONNECTED | write-back epoch of bp (2 bits)
+    uint8_t* pflags;      // per pair: PRESENT | CONNECTED | write-back epoch of bp (4 bits)
     int64_t* expire;      // per pair: retention expiry
     double* bp;           // per pair: behaviourPenalty (as of its epoch: bp_read, gsx_ops.h)
     double* app;          // per pair: AppSpecificScore snapshot (GSX_EV_APP_SCORE updates one)
@@ -123,7 +131,7 @@ struct DevState {
     int64_t last_refresh;  // time of the last refreshScores() (derives meshTime)
     // Deferred write-back of the decayed counters (REC_EPOCH below): refreshes
     // since the last one that stored them (0 .. wb_period - 1), the period
-    // (1, 2 or 4 refreshes; 1 = every refresh stores), and DecayToZero.
+    // (1, 2, 4 or 16 refreshes; 1 = every refresh stores), and DecayToZero.
     uint32_t phase;
     uint32_t wb_period;
     double decay_to_zero;
@@ -135,19 +143,21 @@ constexpr uint8_t REC_ACTIVE = 0x02;
 constexpr uint8_t REC_FRESH = 0x04;  // grafted since the last refresh that covered it: meshTime == 0
 // The write-back epoch of a record: its stored fmd / mmd / mfp / imd are its
 // values as of the refresh at which DevState::phase was this value.  A
-// connected pair's scored record has (phase - epoch) & 3 decays pending
-// (rec_pend, gsx_ops.h); a disconnected pair is never decayed (score.go:503-516)
-// and an unscored topic's record neither, so theirs are always current.
-constexpr uint8_t REC_EPOCH = 0x18;
+// connected pair's scored record has (phase - epoch) & EPOCH_MASK decays
+// pending (rec_pend, gsx_ops.h); a disconnected pair is never decayed
+// (score.go:503-516) and an unscored topic's record neither, so theirs are
+// always current.  Four bits: the phase runs 0 .. 15 under the longest period.
+constexpr uint32_t EPOCH_MASK = 15u;
+constexpr uint8_t REC_EPOCH = 0x78;
 constexpr int REC_EPOCH_SHIFT = 3;
 constexpr uint8_t PAIR_PRESENT = 0x01;
 constexpr uint8_t PAIR_CONNECTED = 0x02;
 // The write-back epoch of a pair's behaviour penalty, by REC_EPOCH's rules: a
 // connected pair's stored bp is its value as of the refresh at which
-// DevState::phase was this value, and (phase - epoch) & 3 decays of d7 pend
-// (bp_pend, gsx_ops.h).  A retained pair is never decayed: nothing pends there.
-// Every reader of the flag byte tests bits, never the whole byte.
-constexpr uint8_t PAIR_EPOCH = 0x0C;
+// DevState::phase was this value, and (phase - epoch) & EPOCH_MASK decays of d7
+// pend (bp_pend, gsx_ops.h).  A retained pair is never decayed: nothing pends
+// there.  Every reader of the flag byte tests bits, never the whole byte.
+constexpr uint8_t PAIR_EPOCH = 0x3C;
 constexpr int PAIR_EPOCH_SHIFT = 2;
 constexpr uint32_t IPG_NONE = 0xFFFFFFFFu;
 constexpr uint32_t IPG_WL = 0x80000000u;  // whitelisted IP: counted, never penalised

@@ -62,6 +62,18 @@ struct DeliveryRecord {
 
 }  // namespace
 
+// The write-back period of a new engine (gsx_set_decay_writeback changes it).
+// A macro so that a measurement can build the library with another default
+// (-DGSX_WB_PERIOD_DEFAULT=4) and compare the periods under one benchmark.
+// tools/pmc.sh profiles "two whole cycles" as 2 x this value, which it asks
+// the library for (gsx_get_decay_writeback of a new engine), not a copy of it.
+#ifndef GSX_WB_PERIOD_DEFAULT
+#define GSX_WB_PERIOD_DEFAULT 16
+#endif
+static_assert(GSX_WB_PERIOD_DEFAULT == 1 || GSX_WB_PERIOD_DEFAULT == 2 || GSX_WB_PERIOD_DEFAULT == 4 ||
+                  GSX_WB_PERIOD_DEFAULT == 16,
+              "the periods gsx_set_decay_writeback accepts");
+
 struct gsx_engine {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -85,7 +97,7 @@ struct gsx_engine {
     // the refresh pass stores them every wb_period-th refresh; phase counts the
     // refreshes since the last one that did (DevState::phase, REC_EPOCH).
     uint32_t phase = 0;
-    uint32_t wb_period = 4;
+    uint32_t wb_period = GSX_WB_PERIOD_DEFAULT;
     // gsx_refresh launches the purge only while a retained pair (present, not
     // connected) can exist.  retain_horizon bounds `expire` of every such pair
     // from above (kRetainUnknown: no bound, always launch); the sites that make
@@ -820,6 +832,11 @@ gsx::DevTopicParams dev_topic_params(const gsx_engine* e, uint32_t t) {
     d.w4 = p.invalid_message_deliveries_weight;
     d.d4 = p.invalid_message_deliveries_decay;
     d.scored = e->scored[t] ? 1 : 0;
+    // (the decay chain's precondition, gsx_ops.h: a decay whose weight is zero is not validated)
+    d.chain = gsx::decay_chain_ok(d.d2) && gsx::decay_chain_ok(d.d3) && gsx::decay_chain_ok(d.d3b) &&
+                      gsx::decay_chain_ok(d.d4)
+                  ? 1
+                  : 0;
     return d;
 }
 
@@ -2478,12 +2495,20 @@ int gsx_refresh(gsx_engine* e, int64_t now) {
 
 int gsx_set_decay_writeback(gsx_engine* e, uint32_t k) {
     if (!e) return GSX_EINVAL;
-    if (k != 1 && k != 2 && k != 4) return fail(e, GSX_EINVAL, "decay write-back period must be 1, 2 or 4");
+    // (8 is not offered: only the periods that were measured are)
+    if (k != 1 && k != 2 && k != 4 && k != 16)
+        return fail(e, GSX_EINVAL, "decay write-back period must be 1, 2, 4 or 16");
     if (int rc = gx_busy(e)) return rc;
     if (int rc = fold_deferred(e)) return rc;
     if (int rc = flush(e)) return rc;
     if (int rc = materialize_all(e)) return rc;
     e->wb_period = k;
+    return GSX_OK;
+}
+
+int gsx_get_decay_writeback(gsx_engine* e, uint32_t* k) {
+    if (!e || !k) return GSX_EINVAL;
+    *k = e->wb_period;
     return GSX_OK;
 }
 

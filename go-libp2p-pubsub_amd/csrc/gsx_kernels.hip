@@ -74,6 +74,8 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
     const bool lag = st & PAIR_CONNECTED;
     // what a connected pair's flag byte keeps at a refresh
     const uint8_t keep_conn = (uint8_t)~(REC_FRESH | (wb ? REC_EPOCH : 0));
+    // the decay chain's precondition on DecayToZero (gsx_ops.h)
+    const bool chain_dtz = pp.decay_to_zero > 0.0;
     double* const tile = s.rec + (p / TILE) * (uint64_t)T * (NFIELD * TILE) + lane;
     uint8_t* const ftile = s.rflags + (p / TILE) * (uint64_t)T * TILE + lane;
     double score = 0.0;
@@ -83,24 +85,45 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
                           int64_t graft, uint8_t fl, uint32_t zmt) {
         double* const r = tile + (uint64_t)t * (NFIELD * TILE);
         const double fmd0 = fmd, mmd0 = mmd, mfp0 = mfp, imd0 = imd;
-        // the pending decays, and this refresh's: the same multiply and compare
-        // in the same order as a store after each would have seen.  When every
-        // lane has the same count the loop is counted in a scalar register,
-        // with no per-lane mask to keep; the counts differ only where an event
-        // touched a lane's record since the last store, or the wave mixes
-        // connected and retained pairs.
-        const uint32_t nd = (lag ? (phase - ((uint32_t)fl >> REC_EPOCH_SHIFT)) & 3u : 0u) + (conn ? 1u : 0u);
+        // the pending decays, and this refresh's, as the decay chain
+        // (gsx_ops.h): the multiplies a store after each refresh would have
+        // seen, in the same order, and one zero test per counter after them
+        // (none for a record with no decay to take).  When every lane has the
+        // same count the loop is counted in a scalar register, with no
+        // per-lane mask to keep; the counts differ only where an event touched
+        // a lane's record since the last store, or the wave mixes connected
+        // and retained pairs.  A topic with a decay outside (0, 1) (one whose
+        // weight is zero: the host validates the others) tests after every
+        // multiply, as does an engine whose DecayToZero is not positive.
+        const uint32_t nd = (lag ? (phase - ((uint32_t)fl >> REC_EPOCH_SHIFT)) & EPOCH_MASK : 0u) + (conn ? 1u : 0u);
         const uint32_t nd0 = __builtin_amdgcn_readfirstlane(nd);
-        auto decay_all = [&]() {
-            fmd = decay(fmd, tp.d2, pp.decay_to_zero);
-            mmd = decay(mmd, tp.d3, pp.decay_to_zero);
-            mfp = decay(mfp, tp.d3b, pp.decay_to_zero);
-            imd = decay(imd, tp.d4, pp.decay_to_zero);
+        auto mul_all = [&]() {
+            fmd *= tp.d2;
+            mmd *= tp.d3;
+            mfp *= tp.d3b;
+            imd *= tp.d4;
         };
-        if (__ballot(nd != nd0) == 0) {
-            for (uint32_t i = 0; i < nd0; ++i) decay_all();
+        auto test_all = [&](bool any) {
+            fmd = (any && fmd < pp.decay_to_zero) ? 0.0 : fmd;
+            mmd = (any && mmd < pp.decay_to_zero) ? 0.0 : mmd;
+            mfp = (any && mfp < pp.decay_to_zero) ? 0.0 : mfp;
+            imd = (any && imd < pp.decay_to_zero) ? 0.0 : imd;
+        };
+        if (tp.chain && chain_dtz) {
+            if (__ballot(nd != nd0) == 0) {
+#pragma clang loop unroll(disable)
+                for (uint32_t i = 0; i < nd0; ++i) mul_all();
+                if (nd0) test_all(true);
+            } else {
+#pragma clang loop unroll(disable)
+                for (uint32_t i = 0; i < nd; ++i) mul_all();
+                test_all(nd != 0);
+            }
         } else {
-            for (uint32_t i = 0; i < nd; ++i) decay_all();
+            for (uint32_t i = 0; i < nd; ++i) {
+                mul_all();
+                test_all(true);
+            }
         }
         // a counter that decays is written back only if it changed: a zero
         // counter (most peers never send an invalid message, most meshes never
@@ -199,10 +222,18 @@ __global__ __launch_bounds__(256) void k_refresh_score(DevState s, KernParams kp
     // flag byte is not written otherwise.
     const double bp0 = s.bp[p];
     double bp = bp0;
-    const uint32_t nb = (lag ? (phase - ((uint32_t)st >> PAIR_EPOCH_SHIFT)) & 3u : 0u) + (conn ? 1u : 0u);
+    const uint32_t nb = (lag ? (phase - ((uint32_t)st >> PAIR_EPOCH_SHIFT)) & EPOCH_MASK : 0u) + (conn ? 1u : 0u);
     const uint32_t nb0 = __builtin_amdgcn_readfirstlane(nb);
-    if (__ballot(nb != nb0) == 0) {
-        for (uint32_t i = 0; i < nb0; ++i) bp = decay(bp, pp.d7, pp.decay_to_zero);
+    if (decay_chain_ok(pp.d7) && chain_dtz) {  // the decay chain, as for the counters
+        if (__ballot(nb != nb0) == 0) {
+#pragma clang loop unroll(disable)
+            for (uint32_t i = 0; i < nb0; ++i) bp *= pp.d7;
+            if (nb0) bp = bp < pp.decay_to_zero ? 0.0 : bp;
+        } else {
+#pragma clang loop unroll(disable)
+            for (uint32_t i = 0; i < nb; ++i) bp *= pp.d7;
+            bp = (nb && bp < pp.decay_to_zero) ? 0.0 : bp;
+        }
     } else {
         for (uint32_t i = 0; i < nb; ++i) bp = decay(bp, pp.d7, pp.decay_to_zero);
     }

@@ -218,8 +218,8 @@ __device__ __forceinline__ void pzmap_mark_row(const DevState& s, uint64_t lo, u
 // ---- deferred write-back of the decayed counters (REC_EPOCH, gsx_device.h) ----
 // The refresh pass stores the decayed counters only every wb_period-th
 // refresh; in between, a record's stored counters lag by rec_pend() decays.
-// decay() applied k times to the stored value is, bit for bit, what k
-// refreshes with a store after each would have left.  Outside the refresh pass
+// rec_decay(k) of the stored value is, bit for bit, what k refreshes with a
+// store after each would have left.  Outside the refresh pass
 // every access to a counter goes through rec_read (a reader) or
 // rec_materialize (before any read-modify-write).
 struct RecVals {
@@ -228,11 +228,57 @@ struct RecVals {
 
 // decays the stored counters of record (pair flags st, record flags fl) lag by
 __device__ __forceinline__ uint32_t rec_pend(const DevState& s, uint8_t st, uint8_t fl, const DevTopicParams& tp) {
-    return ((st & PAIR_CONNECTED) && tp.scored) ? ((s.phase - ((uint32_t)fl >> REC_EPOCH_SHIFT)) & 3u) : 0u;
+    return ((st & PAIR_CONNECTED) && tp.scored) ? ((s.phase - ((uint32_t)fl >> REC_EPOCH_SHIFT)) & EPOCH_MASK) : 0u;
+}
+
+// ---- the decay chain ------------------------------------------------------------
+// k pending decays as k multiplies and ONE zero test: for 0 < d < 1 and
+// 0 < dtz, x = fl(x * d) taken k >= 1 times and then x < dtz ? 0 : x gives, bit
+// for bit, what decay() applied k times gives.  Both forms run the same
+// multiplies on the same values until the stepwise one zeroes x, so they can
+// differ only in when that happens:
+//   - x >= 0: x * d <= x exactly, and x is representable, so the rounded
+//     product is <= x too (subnormals included).  A value under dtz after
+//     step j is therefore still under it after step k: the last test zeroes
+//     what an earlier one would have, and +0.0 decays to +0.0 in between.  A
+//     value never under dtz on the way is not under it at the end, by the
+//     same monotony, and neither form touches it.
+//   - x < 0 (or -0.0): every product stays <= -0.0 < dtz: the first test and
+//     the last alike give +0.0.
+//   - NaN and +inf fail every test and pass through the same multiplies; -inf
+//     is zeroed like any negative value.
+// k == 0 runs no test: a stored value under dtz that no decay has touched
+// stands (an import may hold one).
+// The preconditions are the host's parameter validation
+// (gsx_validate_peer_params: 0 < DecayToZero < 1; gsx_validate_topic_params
+// and the peer parameters: 0 < decay < 1), but a decay is validated only where
+// its weight is not zero, and an engine without peer parameters has
+// DecayToZero == 0.  With d > 1 a value can climb back over dtz, with d < 0 it
+// changes sign, with dtz <= 0 a -0.0 survives the one test: where
+// DevTopicParams::chain (all four decays of the topic), decay_chain_ok(d7) or
+// dtz > 0 does not hold, the pending decays keep the stepwise form.
+__device__ __forceinline__ double decay_chain(double x, double d, double dtz, uint32_t k) {
+    for (uint32_t i = 0; i < k; ++i) x *= d;
+    return (k && x < dtz) ? 0.0 : x;
 }
 
 __device__ __forceinline__ void rec_decay(RecVals& v, const DevTopicParams& tp, double dtz, uint32_t k) {
-    for (uint32_t i = 0; i < k; ++i) {
+    if (tp.chain && dtz > 0.0) {
+        for (uint32_t i = 0; i < k; ++i) {
+            v.fmd *= tp.d2;
+            v.mmd *= tp.d3;
+            v.mfp *= tp.d3b;
+            v.imd *= tp.d4;
+        }
+        if (k) {
+            v.fmd = v.fmd < dtz ? 0.0 : v.fmd;
+            v.mmd = v.mmd < dtz ? 0.0 : v.mmd;
+            v.mfp = v.mfp < dtz ? 0.0 : v.mfp;
+            v.imd = v.imd < dtz ? 0.0 : v.imd;
+        }
+        return;
+    }
+    for (uint32_t i = 0; i < k; ++i) {  // a decay outside (0, 1): test after every multiply
         v.fmd = decay(v.fmd, tp.d2, dtz);
         v.mmd = decay(v.mmd, tp.d3, dtz);
         v.mfp = decay(v.mfp, tp.d3b, dtz);
@@ -279,7 +325,7 @@ __device__ __forceinline__ uint8_t rec_materialize(const DevState& s, uint64_t p
     const uint8_t fl = s.rflags[fi];
     const uint32_t k = rec_pend(s, st, fl, s.tp[t]);
     if (k) rec_store_decayed(s, p, t, k);
-    const uint8_t nf = (uint8_t)((fl & ~REC_EPOCH) | (s.phase << REC_EPOCH_SHIFT));
+    const uint8_t nf = (uint8_t)((fl & ~REC_EPOCH) | ((s.phase & EPOCH_MASK) << REC_EPOCH_SHIFT));
     if (nf != fl) s.rflags[fi] = nf;
     return nf;
 }
@@ -290,10 +336,13 @@ __device__ __forceinline__ uint8_t rec_materialize(const DevState& s, uint64_t p
 // ---- the behaviour penalty under the same write-back (PAIR_EPOCH, gsx_device.h) ----
 // decays of d7 the stored bp of a pair with flags st lags by
 __device__ __forceinline__ uint32_t bp_pend(const DevState& s, uint8_t st) {
-    return (st & PAIR_CONNECTED) ? ((s.phase - ((uint32_t)st >> PAIR_EPOCH_SHIFT)) & 3u) : 0u;
+    return (st & PAIR_CONNECTED) ? ((s.phase - ((uint32_t)st >> PAIR_EPOCH_SHIFT)) & EPOCH_MASK) : 0u;
 }
 
+// (the decay chain above; BehaviourPenaltyDecay is validated only with a
+// non-zero BehaviourPenaltyWeight, so any other value keeps the stepwise form)
 __device__ __forceinline__ double bp_decay(double bp, double d7, double dtz, uint32_t k) {
+    if (decay_chain_ok(d7) && dtz > 0.0) return decay_chain(bp, d7, dtz, k);
     for (uint32_t i = 0; i < k; ++i) bp = decay(bp, d7, dtz);
     return bp;
 }
@@ -313,7 +362,7 @@ __device__ __forceinline__ uint8_t bp_materialize(const DevState& s, uint64_t p,
         const double o = s.bp[p], v = bp_decay(o, s.d7, s.decay_to_zero, k);
         if (__double_as_longlong(v) != __double_as_longlong(o)) s.bp[p] = v;
     }
-    const uint8_t nf = (uint8_t)((st & ~PAIR_EPOCH) | ((s.phase & 3u) << PAIR_EPOCH_SHIFT));
+    const uint8_t nf = (uint8_t)((st & ~PAIR_EPOCH) | ((s.phase & EPOCH_MASK) << PAIR_EPOCH_SHIFT));
     if (nf != st) s.pflags[p] = nf;
     return nf;
 }
@@ -386,7 +435,7 @@ __device__ __forceinline__ bool scored_topic(const DevState& s, uint64_t p, uint
 __device__ inline void ev_add_peer(const DevState& s, const DevPeerParams& pp, uint64_t p, uint64_t row_lo,
                                    uint64_t row_hi) {  // AddPeer :588-602
     const uint8_t st = s.pflags[p];
-    const uint8_t ep = (uint8_t)(s.phase << REC_EPOCH_SHIFT);  // the records are current as of this phase
+    const uint8_t ep = (uint8_t)((s.phase & EPOCH_MASK) << REC_EPOCH_SHIFT);  // the records are current as of this phase
     if (!(st & PAIR_PRESENT)) {  // new peerStats{topics: {}}
         for (uint32_t t = 0; t < s.n_topics; ++t) {
             const size_t b = rec_index(p, t, s.n_topics, FMD);
@@ -417,7 +466,7 @@ __device__ inline void ev_add_peer(const DevState& s, const DevPeerParams& pp, u
     // a new or reconnecting pair's bp is current as of this phase; a connected
     // pair keeps its epoch
     if (!(st & PAIR_PRESENT) || !(st & PAIR_CONNECTED))
-        s.pflags[p] = (uint8_t)(PAIR_PRESENT | PAIR_CONNECTED | ((s.phase & 3u) << PAIR_EPOCH_SHIFT));
+        s.pflags[p] = (uint8_t)(PAIR_PRESENT | PAIR_CONNECTED | ((s.phase & EPOCH_MASK) << PAIR_EPOCH_SHIFT));
 }
 
 __device__ inline void ev_remove_peer(const DevState& s, const DevPeerParams& pp, uint64_t p, int64_t now) {  // :604-637

@@ -679,6 +679,7 @@ SIGNATURES = {
     "gsx_pair_zero_map_violations": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
     "gsx_pair_zero_map_marked": (C.c_int, [C.c_void_p, C.c_uint32, P(C.c_uint64)]),
     "gsx_set_decay_writeback": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "gsx_get_decay_writeback": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
     "gsx_purge_launches": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
     "gsx_last_refresh_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "gsx_synthesize_state": (C.c_int, [C.c_void_p, P(SynthSpec)]),

@@ -1771,7 +1771,8 @@ class Engine:
         return n.value
 
     def set_decay_writeback(self, k: int) -> None:
-        """gsx_set_decay_writeback: the refresh pass stores the decayed counters every k-th refresh (1, 2, 4)."""
+        """gsx_set_decay_writeback: the refresh pass stores the decayed counters every k-th refresh
+        (1, 2, 4 or 16; 16 by default, 8 is not offered)."""
         self._chk(self.lib.gsx_set_decay_writeback(self.h, k), "gsx_set_decay_writeback")
 
     def zero_map_marked(self) -> int:
@@ -1779,6 +1780,12 @@ class Engine:
         n = C.c_uint64()
         self._chk(self.lib.gsx_zero_map_marked(self.h, C.byref(n)), "gsx_zero_map_marked")
         return n.value
+
+    def decay_writeback(self) -> int:
+        """gsx_get_decay_writeback: the write-back period in force."""
+        k = C.c_uint32()
+        self._chk(self.lib.gsx_get_decay_writeback(self.h, C.byref(k)), "gsx_get_decay_writeback")
+        return k.value
 
     def pair_zero_map_violations(self) -> int:
         """gsx_pair_zero_map_violations: pair-zero-map entries that say zero over a non-zero

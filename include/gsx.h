@@ -575,18 +575,21 @@ int gsx_pair_zero_map_violations(gsx_engine* e, uint64_t* n);
 #define GSX_PZ_P6 1u
 int gsx_pair_zero_map_marked(gsx_engine* e, uint32_t which, uint64_t* n);
 /* How often gsx_refresh stores the decayed counters: every k-th refresh, k in
- * {1, 2, 4} (default 4).  A refresh's scores need the decayed values only in
+ * {1, 2, 4, 16} (default 16; 8 is not offered, and every other value is
+ * GSX_EINVAL).  A refresh's scores need the decayed values only in
  * registers; in between, a record's stored counters lag by up to k - 1 decays,
  * which every reader applies on the fly and every writer (events, credits,
  * heartbeats) settles for its record first, so no result changes: scores,
  * gsx_export_state and every other output are bit-identical for every k.
  * k = 1 stores at every refresh.  Settles every record before switching.
  * A pair's behaviour penalty follows the same period: between stores it lags
- * by the same decays of BehaviourPenaltyDecay, counted in two bits of the
+ * by the same decays of BehaviourPenaltyDecay, counted in four bits of the
  * device's pair flag byte; gsx_export_state applies them as it does the
  * counters', so its pair_flags hold only GSX_PAIR_PRESENT | GSX_PAIR_CONNECTED
  * and its behaviour_penalty the current values. */
 int gsx_set_decay_writeback(gsx_engine* e, uint32_t k);
+/* *k = the period in force (a refused gsx_set_decay_writeback leaves it). */
+int gsx_get_decay_writeback(gsx_engine* e, uint32_t* k);
 /* *n = the launches of the purge of expired retained peers (refreshScores,
  * score.go:503-515) since the overlay was loaded.  gsx_refresh launches it
  * only while a pair that is present and not connected can exist: after a

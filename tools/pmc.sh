@@ -24,14 +24,18 @@ run() {  # run NAME SECONDS COUNTER CMD...
     echo "=== $name $c rc=$rc"
     if [ $rc -ne 0 ]; then tail -n 5 "$O/${name}_$c.log"; exit $rc; fi
 }
+# the write-back period of a new engine of the library under test (gsx_get_decay_writeback;
+# GSX_WB_PERIOD_DEFAULT of its build), so that the headline run covers whole cycles
+PERIOD=$(timeout -k 10 60 python3 -c 'import sys; sys.path.insert(0, "go-libp2p-pubsub_amd"); import gsx; print(gsx.Engine(1).decay_writeback())') || exit 2
+case "$PERIOD" in 1|2|4|16) ;; *) echo "write-back period '$PERIOD'?"; exit 2;; esac
 # PMC_SECTIONS="calib hb": only those runs (tools/pmc_bytes.py then merges them
 # into the summary named by PMC_MERGE, e.g. profiles/pmc_r05.json)
 want() { [ -z "${PMC_SECTIONS:-}" ] || [[ " $PMC_SECTIONS " == *" $1 "* ]]; }
 for C in FETCH_SIZE WRITE_SIZE; do
     want calib && run calib 120 $C ./tools/microbench/pmc_calib
-    # 8 launches: two whole write-back cycles of the default period (gsx_set_decay_writeback), so the
-    # per-launch average weighs storing and non-storing refreshes as a long run does
-    want head && run head 300 $C python3 bench.py --steps 7 --warmup 1 --no-cpu --no-dropin --no-single-observer --prop-msgs 0 \
+    # 2 x period launches (PERIOD: the library's own default period, above): two whole write-back
+    # cycles, so the per-launch average weighs storing and non-storing refreshes as a long run does
+    want head && run head 300 $C python3 bench.py --steps $((2 * PERIOD - 1)) --warmup 1 --no-cpu --no-dropin --no-single-observer --prop-msgs 0 \
         --prop-peers 0 --hb-steps 0 --adv-peers 0
     want p1024 && run p1024 200 $C python3 tools/prop_profile.py --msgs 1024 --batches 3 --warmup 2
     want p64 && run p64 200 $C python3 tools/prop_profile.py --msgs 64 --batches 3 --warmup 2
