@@ -127,6 +127,7 @@ struct orc_engine {
     uint32_t mc_n; /* windows alive (history[0..mc_n-1]) */
     uint32_t* ihave_len;   /* [t][pair] of the last heartbeat */
     uint64_t* ihave_hash;
+    uint8_t* ihave_sent;   /* an IHAVE went out, were its list empty (MaxIHaveLength 0, gossipsub.go:1712-1720) */
     /* the last heartbeat's tracer Graft / Prune calls, topic bits per pair
      * (gsx_hb_trace_words): sent GRAFT, sent PRUNE, accepted GRAFT, handled PRUNE */
     uint64_t *tr_sg, *tr_sp, *tr_ag, *tr_hp;
@@ -369,6 +370,7 @@ void orc_destroy(orc_engine* o) {
     free(o->mc);
     free(o->ihave_len);
     free(o->ihave_hash);
+    free(o->ihave_sent);
     free(o->tr_sg);
     free(o->tr_sp);
     free(o->tr_ag);
@@ -436,9 +438,11 @@ int orc_load_overlay(orc_engine* o, uint32_t n_nodes, const int64_t* row_ptr, co
     if (!o->backoff) return GSX_ENOMEM;
     free(o->ihave_len);
     free(o->ihave_hash);
+    free(o->ihave_sent);
     o->ihave_len = (uint32_t*)calloc((size_t)o->T * (E ? E : 1), sizeof(uint32_t));
     o->ihave_hash = (uint64_t*)calloc((size_t)o->T * (E ? E : 1), sizeof(uint64_t));
-    if (!o->ihave_len || !o->ihave_hash) return GSX_ENOMEM;
+    o->ihave_sent = (uint8_t*)calloc((size_t)o->T * (E ? E : 1), 1);
+    if (!o->ihave_len || !o->ihave_hash || !o->ihave_sent) return GSX_ENOMEM;
     free(o->peerhave);
     free(o->iasked);
     free(o->sub);
@@ -1189,12 +1193,22 @@ typedef struct {
     uint32_t k;
 } orc_rng;
 static int32_t rng_int31(orc_rng* g) { return (int32_t)(h4(g->seed, g->tag, g->vertex, g->base | g->k++) >> 33); }
+static uint64_t rng_rejects[ORC_RNG_TAGS]; /* process-wide, by draw tag (slot 0: any tag >= ORC_RNG_TAGS) */
 static int32_t rng_int31n(orc_rng* g, int32_t n) {
     if ((n & (n - 1)) == 0) return rng_int31(g) & (n - 1);
     int32_t max = (int32_t)((1u << 31) - 1 - (1u << 31) % (uint32_t)n);
     int32_t v = rng_int31(g);
-    while (v > max) v = rng_int31(g);
+    while (v > max) { /* the rejected draws per tag, for the tests that pin this branch */
+        __atomic_fetch_add(&rng_rejects[g->tag < ORC_RNG_TAGS ? g->tag : 0], 1, __ATOMIC_RELAXED);
+        v = rng_int31(g);
+    }
     return v % n;
+}
+void orc_rng_rejections(uint64_t* out) {
+    for (int i = 0; i < ORC_RNG_TAGS; i++) out[i] = __atomic_load_n(&rng_rejects[i], __ATOMIC_RELAXED);
+}
+void orc_rng_rejections_reset(void) {
+    for (int i = 0; i < ORC_RNG_TAGS; i++) __atomic_store_n(&rng_rejects[i], 0, __ATOMIC_RELAXED);
 }
 /* shufflePeers, gossipsub.go:1890-1895 */
 static void shuffle_pairs(uint64_t* a, int n, orc_rng* g) {
@@ -1823,6 +1837,7 @@ static void emit_gossip(hb_ctx* c, uint32_t v, uint32_t t, orc_rng* g, uint64_t*
         }
         o->ihave_len[x] = (uint32_t)len;
         o->ihave_hash[x] = d;
+        o->ihave_sent[x] = 1;
         c->out->ihave_msgs++;
         c->out->ihave_ids += len;
     }
@@ -2085,7 +2100,7 @@ static int gossip_exchange(orc_engine* o, const gsx_gossipsub_params* gp, uint64
             if (r < 0) continue;
             uint64_t tb = 0;
             for (uint32_t t = 0; t < T; t++)
-                if (o->ihave_len[(size_t)t * E + r]) tb |= 1ull << t;
+                if (o->ihave_sent[(size_t)t * E + r]) tb |= 1ull << t;
             if (!tb) continue;
             const uint32_t v = (uint32_t)o->col[q];
             size_t n = 0;
@@ -2672,6 +2687,7 @@ int orc_heartbeat(orc_engine* o, const gsx_gossipsub_params* gp, uint64_t tick, 
     }
     memset(o->ihave_len, 0, sizeof(uint32_t) * (size_t)T * (E ? E : 1));
     memset(o->ihave_hash, 0, sizeof(uint64_t) * (size_t)T * (E ? E : 1));
+    memset(o->ihave_sent, 0, (size_t)T * (E ? E : 1));
     /* (A) every node's heartbeat, every joined topic in ascending order:
      * mesh maintenance, then IHAVE gossip, one draw stream per (node, topic) */
     for (uint32_t v = 0; v < o->n_nodes; v++) {

@@ -82,6 +82,12 @@ int orc_promise_broken(orc_engine* o, int64_t now, uint32_t* counts, uint64_t* t
 int orc_promise_fulfill(orc_engine* o, uint32_t node, uint64_t handle);
 int orc_promise_throttle(orc_engine* o, uint64_t pair);
 int orc_promise_count(orc_engine* o, uint64_t* n);
+/* Rejected Int31n draws (Go's `for v > max` redraw) since the last reset, per
+ * draw tag of the counter hash: process-wide, every engine and thread adds to
+ * them.  For tests that must know a run took the redraw branch. */
+#define ORC_RNG_TAGS 16
+void orc_rng_rejections(uint64_t* out); /* ORC_RNG_TAGS counts */
+void orc_rng_rejections_reset(void);
 int orc_mcache_clear(orc_engine* o);
 int orc_mcache_last(orc_engine* o, uint32_t* n_msgs);
 /* hop_rows (may be NULL): the set's arrival hops ([node][message] bytes, the

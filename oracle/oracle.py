@@ -77,6 +77,8 @@ _SIG = {
     "orc_promise_fulfill": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64]),
     "orc_promise_throttle": (C.c_int, [C.c_void_p, C.c_uint64]),
     "orc_promise_count": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
+    "orc_rng_rejections": (None, [P(C.c_uint64)]),
+    "orc_rng_rejections_reset": (None, []),
     "orc_mcache_ids": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint64), C.c_size_t,
                                  P(C.c_size_t)]),
     "orc_mcache_last": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
@@ -431,6 +433,21 @@ class Oracle:
         self._chk(self.lib.orc_export_state(self.h, C.byref(sv)), "orc_export_state")
         out["last_refresh_ns"] = int(sv.last_refresh_ns)
         return out
+
+
+RNG_TAGS = 16  # ORC_RNG_TAGS
+
+
+def rng_rejections() -> Dict[int, int]:
+    """Rejected Int31n draws since the last reset, {draw tag: count} of the
+    tags that have any (process-wide: every Oracle adds to them)."""
+    out = (C.c_uint64 * RNG_TAGS)()
+    load().orc_rng_rejections(out)
+    return {t: int(c) for t, c in enumerate(out) if c}
+
+
+def rng_rejections_reset():
+    load().orc_rng_rejections_reset()
 
 
 # validate / decay twins

@@ -24,11 +24,12 @@ def snapshot(be):
 
 
 def mesh_run(be, n, d, T, seed, ticks, mesh_degree=6, mix=False, direct=0.0, disconnect=0.0, gp=None,
-             prop_msgs=0, first_tick=1, mostly_positive=False, prop_topics=None, pre=None):
+             prop_msgs=0, first_tick=1, mostly_positive=False, prop_topics=None, pre=None, thresholds=None):
     """pc.setup's random mesh, then `ticks` rounds of: heartbeat, optional
     gossipsub propagation with score credits, refresh.  Round k propagates on
     topic k % T, or on prop_topics[k % len(prop_topics)] if given; pre: a list
-    that gets the exported state before the first round.  Returns the per-tick
+    that gets the exported state before the first round; thresholds: set
+    after pc.setup's own.  Returns the per-tick
     counters and snapshots."""
     ov = pc.overlay(n, d, seed, mix_protocols=mix, direct_frac=direct)
     pc.setup(be, ov, T, seed, mesh_degree=mesh_degree, disconnect_frac=disconnect)
@@ -38,6 +39,8 @@ def mesh_run(be, n, d, T, seed, ticks, mesh_degree=6, mix=False, direct=0.0, dis
         be.set_app_scores(np.where(rng.random(E) < 0.08, -500.0, np.abs(rng.normal(0, 2, E))))
     if gp is not None:
         be.set_gossipsub_params(gp)
+    if thresholds is not None:  # (pc.setup's have OpportunisticGraftThreshold 0)
+        be.set_thresholds(thresholds)
     if pre is not None:
         pre.append(be.export_state())
     outs, snaps = [], []
