@@ -105,6 +105,7 @@ struct gsx_engine {
     bool retained_possible = false;
     int64_t retain_horizon = INT64_MIN;
     uint64_t purge_launches = 0;  // since the overlay was loaded
+    uint64_t dropin_launches = 0;  // k_dropin launches since the overlay was loaded
     std::vector<int64_t> row_ptr;
     std::vector<int32_t> col_host;
     std::vector<uint32_t> pair_obs;
@@ -1952,6 +1953,7 @@ int load_overlay(gsx_engine* e, uint32_t n_total, uint32_t node_lo, uint32_t n_n
     e->retained_possible = false;  // (the pair flags start all zero)
     e->retain_horizon = INT64_MIN;
     e->purge_launches = 0;
+    e->dropin_launches = 0;
     e->row_ptr.assign(row_ptr, row_ptr + n_nodes + 1);
     e->col_host.assign(col, col + E);
     e->pair_obs.resize(E);
@@ -2646,6 +2648,7 @@ int dropin_fast(gsx_engine* e) {
                                  reinterpret_cast<const uint32_t*>(e->d_dropin + ob_off), (uint32_t)rows.size(),
                                  reinterpret_cast<const uint64_t*>(e->d_dropin + pr_off), (uint32_t)prs.size(),
                                  e->d_row_ptr, e->h_score_dev, reinterpret_cast<uint32_t*>(e->d_dropin), tag, e->stream));
+    ++e->dropin_launches;
     pending_clear(e);
     const volatile uint32_t* flag = static_cast<const volatile uint32_t*>(e->h_dropin);
     const auto t0 = std::chrono::steady_clock::now();
@@ -2955,6 +2958,13 @@ int gsx_purge_launches(gsx_engine* e, uint64_t* n) {
     if (!e || !n) return GSX_EINVAL;
     if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
     *n = e->purge_launches;
+    return GSX_OK;
+}
+
+int gsx_dropin_launches(gsx_engine* e, uint64_t* n) {
+    if (!e || !n) return GSX_EINVAL;
+    if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
+    *n = e->dropin_launches;
     return GSX_OK;
 }
 

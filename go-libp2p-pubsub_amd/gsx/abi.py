@@ -681,6 +681,7 @@ SIGNATURES = {
     "gsx_set_decay_writeback": (C.c_int, [C.c_void_p, C.c_uint32]),
     "gsx_get_decay_writeback": (C.c_int, [C.c_void_p, P(C.c_uint32)]),
     "gsx_purge_launches": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
+    "gsx_dropin_launches": (C.c_int, [C.c_void_p, P(C.c_uint64)]),
     "gsx_last_refresh_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "gsx_synthesize_state": (C.c_int, [C.c_void_p, P(SynthSpec)]),
     "gsx_propagate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, P(PropConfig), P(PropOut)]),

@@ -1805,3 +1805,10 @@ class Engine:
         n = C.c_uint64()
         self._chk(self.lib.gsx_purge_launches(self.h, C.byref(n)), "gsx_purge_launches")
         return n.value
+
+    def dropin_launches(self) -> int:
+        """gsx_dropin_launches: launches of the drop-in round trip (score / score_many on a small
+        engine whose host score copy was current) since the overlay was loaded."""
+        n = C.c_uint64()
+        self._chk(self.lib.gsx_dropin_launches(self.h, C.byref(n)), "gsx_dropin_launches")
+        return n.value

@@ -596,6 +596,13 @@ int gsx_get_decay_writeback(gsx_engine* e, uint32_t* k);
  * RemovePeer, an imported state that holds one, or a synthesized state with
  * p_disconnected > 0, until a refresh later than every such pair's expiry. */
 int gsx_purge_launches(gsx_engine* e, uint64_t* n);
+/* *n = the launches of the drop-in round trip (one kernel applies the queued
+ * events and re-scores what they change into both score copies) since the
+ * overlay was loaded.  gsx_score / gsx_score_many take it on an engine of at
+ * most 65,536 pairs whose host score copy is current, for at most 4,096
+ * queued events of at most 64 observers that touch a pair asked for; every
+ * other read of scores goes through the general path and leaves *n alone. */
+int gsx_dropin_launches(gsx_engine* e, uint64_t* n);
 
 /* WithPeerScoreInspect's extended view (ExtendedPeerScoreInspectFn,
  * inspectScoresExtended score.go:463-493): a PeerScoreSnapshot per pair

@@ -2,7 +2,9 @@
 any backend (HIP engine or CPU oracle) so their results can be compared
 bit-for-bit.  Covers every event kind, every tracer call and reject reason,
 retention/expiry, IP colocation with a whitelist, app scores, topic-param
-resets with recap, an unscored topic, and delivery-record gc."""
+resets with recap, an unscored topic, and delivery-record gc.  session_ops /
+session_replay add what a router does around them: large event batches,
+credited propagation batches, heartbeats and Score() reads in between."""
 from __future__ import annotations
 
 import numpy as np
@@ -241,3 +243,110 @@ def interleaved_score_calls(be, ov, n_topics, ops, seed, per_call=2, many=False)
             be.set_pair_ips(op[1], op[2])
             ask()
     return np.array(out)
+
+
+def _op_now(op, now):
+    k = op[0]
+    if k == "events" and op[1]:
+        return max(now, max(e[3] for e in op[1]))
+    if k == "trace" and op[1]:
+        return max(now, max(c[-1] for c in op[1]))
+    if k == "refresh":
+        return max(now, op[1])
+    return now
+
+
+def session_ops(ov, n_topics, seed, n_steps=150):
+    """make_ops plus what a router does around it: larger event batches (1 .. 200 events over
+    1 .. 80 observers), gossipsub / floodsub batches of 24 .. 96 messages with credits,
+    heartbeats, Score() of one pair and of 1 .. 40 pairs, and an occasional scores()."""
+    import propagation_cases as pc
+
+    rng = np.random.default_rng(seed + 2)
+    E = ov.n_pairs
+    rows = [np.arange(ov.row_ptr[i], ov.row_ptr[i + 1]) for i in range(ov.n)]
+    busy = [i for i in range(ov.n) if len(rows[i])]
+    ops, now, tick, batch = [], T0, 0, 0
+    for op in make_ops(ov, n_topics, seed, n_steps):
+        ops.append(op)
+        now = _op_now(op, now)
+        r = rng.random()
+        if r < 0.12:
+            who = rng.choice(busy, int(rng.integers(1, 81)))
+            evs = []
+            for _ in range(int(rng.integers(1, 201))):
+                kind = int(rng.integers(1, 10))
+                p = int(rng.choice(rows[int(rng.choice(who))]))
+                arg = 0
+                if kind == abi.EV_PENALTY:
+                    arg = int(rng.integers(1, 4))
+                elif kind == abi.EV_APP_SCORE:
+                    arg = int(np.float64(rng.normal(0, 3)).view(np.int64))
+                evs.append((kind, int(rng.integers(0, n_topics)), p, now, arg))
+            ops.append(("events", evs))
+        elif r < 0.22:
+            batch += 1
+            router = abi.GSX_ROUTER_GOSSIPSUB if rng.random() < 0.7 else abi.GSX_ROUTER_FLOODSUB
+            ms = pc.messages(ov.n, int(rng.integers(24, 97)), seed * 1000 + batch, invalid=0.1)
+            cfg = pc.config(router, topic=int(rng.integers(0, n_topics)), latency_ms=int(rng.choice([0, 5, 10])),
+                            seed=seed + batch)
+            cfg.now_ns = now
+            ops.append(("propagate", ms, cfg))
+        elif r < 0.28:
+            tick += 1
+            ops.append(("heartbeat", tick, now, seed + tick))
+        elif r < 0.55:
+            ops.append(("score", int(rng.integers(0, E))))
+        elif r < 0.80:
+            ops.append(("score_many", rng.integers(0, E, int(rng.integers(1, 41))).astype(np.uint64)))
+        elif r < 0.84:
+            ops.append(("scores",))
+    return ops
+
+
+def session_replay(be, ov, n_topics, ops, whitelist=(3,)):
+    """Replays session_ops' calls on one backend.  -> [(kind, value)] of everything read: each
+    Score() answer, the counters of each propagation and heartbeat, and at a check the scores,
+    the exported state and the number of delivery records."""
+    pp, tps = scenario_params(n_topics)
+    be.set_peer_params(pp)
+    for t, tp in tps.items():
+        be.set_topic_params(t, tp)
+    be.load_overlay(ov.row_ptr, ov.col, ov.edge_flags, ov.node_ips)
+    be.set_ip_whitelist(list(whitelist))
+    reads = []
+    for op in ops:
+        k = op[0]
+        if k == "events":
+            be.apply_events(np.array(op[1], dtype=abi.event_dtype()))
+        elif k == "trace":
+            for c in op[1]:
+                getattr(be, "trace_" + c[0])(*c[1:])
+        elif k == "refresh":
+            be.refresh(op[1])
+        elif k == "app":
+            be.set_app_scores(op[1])
+        elif k == "topic_params":
+            be.set_topic_params(op[1], op[2])
+        elif k == "gc":
+            be.gc_deliveries(op[1])
+        elif k == "ips":
+            be.set_pair_ips(op[1], op[2])
+        elif k == "propagate":
+            out = be.propagate(op[1], op[2])[0].as_dict()
+            reads.append((k, {f: np.int64(v) for f, v in out.items()}))
+        elif k == "heartbeat":
+            out = be.heartbeat(op[1], op[2], op[3]).as_dict()
+            reads.append((k, {f: np.int64(v) for f, v in out.items()}))
+        elif k == "score":
+            reads.append((k, np.float64(be.score(op[1]))))
+        elif k == "score_many":
+            reads.append((k, np.array(be.score_many(op[1]), dtype=np.float64)))
+        elif k == "scores":
+            reads.append((k, np.array(be.scores())))
+        elif k == "check":
+            reads.append(("check scores", np.array(be.scores())))
+            st = be.export_state()
+            reads.append(("check state", {f: np.asarray(st[f]) for f in abi.STATE_FIELDS}))
+            reads.append(("check records", np.int64(be.num_delivery_records())))
+    return reads

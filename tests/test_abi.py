@@ -71,6 +71,19 @@ def test_null_engine_is_einval():
     assert lib.gsx_destroy(None) == 0
 
 
+def test_launch_counters_share_a_signature_and_refuse_null():
+    """gsx_purge_launches and gsx_dropin_launches: (engine, uint64*) -> int, declared, bound and
+    wrapped by Engine; a null engine or a null result is GSX_EINVAL before any device work."""
+    lib = gsx.load_library()
+    n = C.c_uint64(7)
+    for name in ("gsx_purge_launches", "gsx_dropin_launches"):
+        assert name in declared_functions()
+        assert abi.SIGNATURES[name] == (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)])
+        assert getattr(lib, name)(None, C.byref(n)) == abi.GSX_EINVAL
+        assert n.value == 7
+        assert callable(getattr(gsx.Engine, name[len("gsx_"):]))
+
+
 @pytest.mark.parametrize("case", VAL["validation"], ids=[c["ref"] for c in VAL["validation"]])
 def test_engine_params_validation(case):
     lib = gsx.load_library()
