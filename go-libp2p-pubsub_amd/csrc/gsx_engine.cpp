@@ -74,6 +74,31 @@ static_assert(GSX_WB_PERIOD_DEFAULT == 1 || GSX_WB_PERIOD_DEFAULT == 2 || GSX_WB
                   GSX_WB_PERIOD_DEFAULT == 16,
               "the periods gsx_set_decay_writeback accepts");
 
+struct gsx_engine;
+
+namespace {
+// A staging buffer: the device side of a result that goes to host memory, or a
+// call's device scratch.  It belongs to the state struct it is a member of and
+// goes with it: resetting the struct (`= {}`) frees the block.
+template <class T>
+struct StageBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // elements
+    StageBuf() = default;
+    StageBuf(StageBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    StageBuf& operator=(StageBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~StageBuf() {
+        if (p) (void)hipFree(p);
+    }
+    // Room for n elements: nothing when cap >= n, else a new block (contents are not kept).
+    int reserve(gsx_engine* e, size_t n);
+};
+}  // namespace
+
 struct gsx_engine {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -436,38 +461,30 @@ struct gsx_engine {
         uint64_t halo_cap = 0, hfrom_cap = 0;
         uint32_t halo_words = 0;       // the W the halo's rows were last laid out for (stride W + 1)
         unsigned long long* dcount = nullptr;
-        // gsx_prop_stats: the device side of results that go to host memory (the
-        // histogram grown when m grows, the per-node arrays sized once)
-        uint32_t* st_hist = nullptr;
-        size_t st_hist_cap = 0;
-        uint32_t* st_recv = nullptr;
-        unsigned long long* st_sum = nullptr;
+        // gsx_prop_stats: the device side of results that go to host memory
+        StageBuf<uint32_t> st_hist, st_recv;
+        StageBuf<unsigned long long> st_sum;
         // gsx_prop_traffic: its scratch rows ([node][word]), the size planes, and the
-        // device side of outputs that go to host memory, each grown on demand
-        uint64_t *tr_sset = nullptr, *tr_planes = nullptr;
-        uint32_t *tr_msg = nullptr, *tr_node = nullptr, *tr_pair = nullptr;
-        unsigned long long *tr_nbytes = nullptr, *tr_pbytes = nullptr;
-        size_t tr_sset_cap = 0, tr_planes_cap = 0, tr_msg_cap = 0, tr_node_cap = 0, tr_pair_cap = 0, tr_nbytes_cap = 0,
-               tr_pbytes_cap = 0;
+        // device side of outputs that go to host memory
+        StageBuf<uint64_t> tr_sset, tr_planes;
+        StageBuf<uint32_t> tr_msg, tr_node, tr_pair;
+        StageBuf<unsigned long long> tr_nbytes, tr_pbytes;
         std::vector<uint64_t> tr_hplanes;  // (host staging of the planes, alive until their upload is done)
         bool tr_planes_busy = false;
         // gsx_score_stats: the same for its five outputs, each sized once for
         // GSX_SS_MAX_EDGES + 1 bins (per node, never per pair)
-        unsigned long long* ss_hist = nullptr;
-        uint32_t *ss_obs_bins = nullptr, *ss_peer_bins = nullptr;
-        unsigned long long *ss_obs_min = nullptr, *ss_peer_min = nullptr;
+        StageBuf<unsigned long long> ss_hist, ss_obs_min, ss_peer_min;
+        StageBuf<uint32_t> ss_obs_bins, ss_peer_bins;
         // gsx_score_parts: the same for its four tables (the pair outputs are staged per call)
-        unsigned long long *sp_cause_hist = nullptr, *sp_topic_hist = nullptr;
-        uint32_t *sp_obs_cause = nullptr, *sp_peer_cause = nullptr;
-        // gsx_mesh_stats: the small tables in one block, the four [topic][node] tables
+        StageBuf<unsigned long long> sp_cause_hist, sp_topic_hist;
+        StageBuf<uint32_t> sp_obs_cause, sp_peer_cause;
+        // gsx_mesh_stats: the six small tables, the four [topic][node] tables
         // (degree, outbound, in-degree, honest degree: the user's where given, else
         // these, which pass 2 reads), the class degrees, the fanout words and the
         // classes of a host array; each sized once for the overlay, kept across calls
-        unsigned long long* ms_tab = nullptr;
-        uint32_t* ms_node[4] = {nullptr, nullptr, nullptr, nullptr};
-        uint32_t* ms_ncd = nullptr;
-        unsigned long long* ms_fan = nullptr;
-        uint8_t* ms_class = nullptr;
+        StageBuf<unsigned long long> ms_tab[6], ms_fan;
+        StageBuf<uint32_t> ms_node[4], ms_ncd;
+        StageBuf<uint8_t> ms_class;
         std::vector<uint8_t> ms_hclass;  // (host staging of the classes, alive until their upload is done)
         bool ms_class_busy = false;
     } prop;
@@ -495,18 +512,14 @@ struct gsx_engine {
         bool have = false;   // a timed call's results are held
         bool after = false;  // the last propagation was a timed call: gsx_propagate's result rows are not its
         hipEvent_t ev[2] = {nullptr, nullptr};
-        uint32_t* st_hist = nullptr;
-        size_t st_hist_cap = 0;
-        uint32_t* st_recv = nullptr;
-        unsigned long long* st_sum = nullptr;
+        // gsx_timed_stats: the device side of results that go to host memory
+        StageBuf<uint32_t> st_hist, st_recv;
+        StageBuf<unsigned long long> st_sum;
         // gsx_timed_traffic: valid while the latencies are the call's; the sizes on the device and
-        // the device side of outputs that go to host memory, each grown on demand
+        // the device side of outputs that go to host memory
         bool lat_kept = false;
-        uint32_t *tt_sizes = nullptr, *tt_msg = nullptr, *tt_node = nullptr, *tt_pair = nullptr, *tt_pkbin = nullptr;
-        unsigned long long *tt_nbytes = nullptr, *tt_pbytes = nullptr, *tt_bins = nullptr, *tt_bbytes = nullptr,
-                           *tt_peak = nullptr;
-        size_t tt_sizes_cap = 0, tt_msg_cap = 0, tt_node_cap = 0, tt_pair_cap = 0, tt_pkbin_cap = 0, tt_nbytes_cap = 0,
-               tt_pbytes_cap = 0, tt_bins_cap = 0, tt_bbytes_cap = 0, tt_peak_cap = 0;
+        StageBuf<uint32_t> tt_sizes, tt_msg, tt_node, tt_pair, tt_pkbin;
+        StageBuf<unsigned long long> tt_nbytes, tt_pbytes, tt_bins, tt_bbytes, tt_peak;
         std::vector<uint32_t> tt_hsizes;  // (host staging of the sizes, alive until their upload is done)
         bool tt_sizes_busy = false;
     } tprop;
@@ -524,9 +537,8 @@ struct gsx_engine {
         uint32_t groups = 0;           // allocated gater groups (n_nodes + n_groups as of the last growth)
         uint8_t* decision = nullptr;   // [pair] the last full gsx_accept_from
         bool have_decision = false;
-        uint8_t* list_out = nullptr;   // a listed call's pairs and bytes (grown)
-        uint64_t* list_pairs = nullptr;
-        size_t list_cap = 0;
+        StageBuf<uint8_t> list_out;    // a listed call's bytes and pairs (grown together)
+        StageBuf<uint64_t> list_pairs;
         void* ev = nullptr;            // gsx_gater_events' device staging (grown)
         size_t ev_bytes = 0;
         uint32_t *gcnt = nullptr, *ocnt = nullptr;  // gsx_gater_fold_prop's counts (zero between calls)
@@ -555,8 +567,8 @@ struct gsx_engine {
         uint32_t* long_rows = nullptr; // rows above CONN_LONG_ROW pairs
         uint32_t n_long = 0;
         // the device side of results that go to host memory (each sized once)
-        uint32_t *val_buf = nullptr, *nt_buf = nullptr;
-        uint8_t *prot_buf = nullptr, *trim_buf = nullptr, *exp_buf = nullptr;
+        StageBuf<uint32_t> val_buf, nt_buf;
+        StageBuf<uint8_t> prot_buf, trim_buf, exp_buf;
         std::map<std::pair<uint32_t, uint64_t>, std::vector<uint64_t>> near;  // (observer, msg_id) -> pairs
     } tagt;
 
@@ -1054,7 +1066,7 @@ void gx_abort(gsx_engine* e) {
 void gater_free(gsx_engine* e) {
     auto& G = e->gater;
     void* gp[] = {G.validate, G.throttle,   G.ctr,        G.last, G.expire, G.hot,  G.connected, G.bind,
-                  G.decision, G.list_out,   G.list_pairs, G.ev,   G.gcnt,   G.ocnt, G.fold_buf};
+                  G.decision, G.ev,         G.gcnt,       G.ocnt, G.fold_buf};
     for (void* p : gp)
         if (p) (void)hipFree(p);
     G = {};
@@ -1065,7 +1077,7 @@ void gater_free(gsx_engine* e) {
 // Frees the tag tracer: its tags, buffers and pending messages.
 void tag_free(gsx_engine* e) {
     auto& G = e->tagt;
-    void* tp[] = {G.tags, G.ev, G.fold_buf, G.key, G.long_rows, G.val_buf, G.nt_buf, G.prot_buf, G.trim_buf, G.exp_buf};
+    void* tp[] = {G.tags, G.ev, G.fold_buf, G.key, G.long_rows};
     for (void* p : tp)
         if (p) (void)hipFree(p);
     G = {};
@@ -1074,9 +1086,7 @@ void tag_free(gsx_engine* e) {
 void timed_free(gsx_engine* e) {
     auto& T = e->tprop;
     void* pp[] = {T.lat, T.fwd, T.rfwd, T.pin, T.cend, T.chg, T.nchg, T.cent, T.ndirty, T.gray_pairs, T.stats, T.fcnt,
-                  T.dcnt, T.icnt, T.ring, T.rocc, T.mark, T.seen, T.origin, T.from, T.vmask, T.arr, T.msgs, T.st_hist,
-                  T.st_recv, T.st_sum, T.tt_sizes, T.tt_msg, T.tt_node, T.tt_pair, T.tt_pkbin, T.tt_nbytes, T.tt_pbytes,
-                  T.tt_bins, T.tt_bbytes, T.tt_peak};
+                  T.dcnt, T.icnt, T.ring, T.rocc, T.mark, T.seen, T.origin, T.from, T.vmask, T.arr, T.msgs};
     for (void* p : pp)
         if (p) (void)hipFree(p);
     hipEvent_t ev[2] = {T.ev[0], T.ev[1]};
@@ -1135,14 +1145,7 @@ void free_state(gsx_engine* e) {
                   e->prop.cent, e->prop.cend, e->prop.chg, e->prop.nchg, e->prop.ndirty, e->prop.rfwd,
                   e->d_halo_pair, e->d_send_slot, e->d_rmark_v, e->d_rmark_u, e->prop.front_g, e->prop.occ_g,
                   e->prop.src_bits, e->prop.src_ids, e->prop.src_rows,
-                  e->prop.d_dig, e->prop.rcand, e->prop.tterm, e->prop.tgen, e->prop.hist_alt, e->prop.occ_alt,
-                  e->prop.st_hist, e->prop.st_recv, e->prop.st_sum,
-                  e->prop.tr_sset, e->prop.tr_planes, e->prop.tr_msg, e->prop.tr_node, e->prop.tr_pair,
-                  e->prop.tr_nbytes, e->prop.tr_pbytes,
-                  e->prop.ss_hist, e->prop.ss_obs_bins, e->prop.ss_peer_bins, e->prop.ss_obs_min, e->prop.ss_peer_min,
-                  e->prop.sp_cause_hist, e->prop.sp_topic_hist, e->prop.sp_obs_cause, e->prop.sp_peer_cause,
-                  e->prop.ms_tab, e->prop.ms_node[0], e->prop.ms_node[1], e->prop.ms_node[2], e->prop.ms_node[3],
-                  e->prop.ms_ncd, e->prop.ms_fan, e->prop.ms_class};
+                  e->prop.d_dig, e->prop.rcand, e->prop.tterm, e->prop.tgen, e->prop.hist_alt, e->prop.occ_alt};
     for (void* p : pp)
         if (p) (void)hipFree(p);
     std::vector<hipEvent_t> evs = std::move(e->prop.ev);
@@ -1277,6 +1280,20 @@ template <class T>
 int dalloc(gsx_engine* e, T** p, size_t n) {
     hipError_t st = hipMalloc((void**)p, sizeof(T) * (n ? n : 1));
     if (st != hipSuccess) return fail(e, GSX_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(st));
+    return GSX_OK;
+}
+
+template <class T>
+int StageBuf<T>::reserve(gsx_engine* e, size_t n) {
+    if (cap >= n) return GSX_OK;
+    if (p) {
+        HIPCHK(e, hipStreamSynchronize(e->stream));  // (work in flight may still write the old block)
+        (void)hipFree(p);
+    }
+    p = nullptr;
+    cap = 0;
+    if (int rc = dalloc(e, &p, n)) return rc;
+    cap = n;
     return GSX_OK;
 }
 
@@ -4210,6 +4227,80 @@ bool on_device(const void* p) {
     return a.type == hipMemoryTypeDevice;
 }
 
+extern "C++" {
+namespace {
+// gsx_timing_begin: the launches between begin() and end() are one timed launch.
+struct LaunchRegion {
+    gsx_engine* e;
+    bool on;
+    explicit LaunchRegion(gsx_engine* e_) : e(e_), on(e_->t_active && e_->t_used < e_->t_max) {}
+    hipError_t begin() { return on ? hipEventRecord(e->tev[2 * e->t_used], e->stream) : hipSuccess; }
+    hipError_t end() {
+        if (!on) return hipSuccess;
+        const hipError_t st = hipEventRecord(e->tev[2 * e->t_used + 1], e->stream);
+        ++e->t_used;
+        return st;
+    }
+};
+
+// The optional outputs of one call, by the rule of gsx.h: NULL is skipped,
+// device memory is written in place in stream order, host memory gets a copy
+// of a staging buffer and the call waits once.  bind() gives the pointer the
+// kernel writes (null: skipped); zero() clears the outputs that asked for it
+// and finish() copies the host ones back, both in bind order.
+struct OutBinder {
+    gsx_engine* e;
+    int rc = GSX_OK;      // the first reserve that failed (every later bind is skipped)
+    bool synced = false;  // finish() waited for the stream
+    struct Out {
+        void* user;  // the host memory to copy back to, null if none
+        void* dev;
+        size_t bytes;
+        bool zeroed;
+    };
+    std::array<Out, 16> outs{};
+    size_t n_outs = 0;
+    explicit OutBinder(gsx_engine* e_) : e(e_) {}
+    // `room`: the elements to reserve when n of them is less (a fixed size that no later call outgrows)
+    template <class T, class U>
+    T* bind(U* user, StageBuf<T>& buf, size_t n, bool zeroed, size_t room = 0) {
+        static_assert(sizeof(T) == sizeof(U), "the staging buffer has the output's element size");
+        if (!user || !n || rc) return nullptr;
+        if (on_device(user)) return note(nullptr, reinterpret_cast<T*>(user), n, zeroed);
+        if ((rc = buf.reserve(e, std::max(n, room)))) return nullptr;
+        return note(user, buf.p, n, zeroed);
+    }
+    // A staging buffer the kernel writes although no output asked for it.
+    template <class T>
+    T* scratch(StageBuf<T>& buf, size_t n, bool zeroed) {
+        if (rc || (rc = buf.reserve(e, n))) return nullptr;
+        return note(nullptr, buf.p, n, zeroed);
+    }
+    int zero() {
+        for (size_t k = 0; k < n_outs; ++k)
+            if (outs[k].zeroed) HIPCHK(e, hipMemsetAsync(outs[k].dev, 0, outs[k].bytes, e->stream));
+        return GSX_OK;
+    }
+    int finish() {
+        for (size_t k = 0; k < n_outs; ++k)
+            if (outs[k].user) {
+                HIPCHK(e, hipMemcpyAsync(outs[k].user, outs[k].dev, outs[k].bytes, hipMemcpyDeviceToHost, e->stream));
+                synced = true;
+            }
+        if (synced) HIPCHK(e, hipStreamSynchronize(e->stream));
+        return GSX_OK;
+    }
+
+private:
+    template <class T>
+    T* note(void* user, T* dev, size_t n, bool zeroed) {
+        outs.at(n_outs++) = Out{user, dev, sizeof(T) * n, zeroed};
+        return dev;
+    }
+};
+}  // namespace
+}  // extern "C++"
+
 int gsx_prop_pending_credits(gsx_engine* e, uint32_t* first, uint32_t* dup) {
     if (!e) return GSX_EINVAL;
     if (!e->loaded || !e->prop.first) return fail(e, GSX_ESTATE, "no propagation yet");
@@ -4310,85 +4401,19 @@ int gsx_prop_stats(gsx_engine* e, uint32_t* msg_hop_hist, uint32_t* node_receive
     const size_t m = ps.n_msgs, N = ps.n_nodes;
     if (m == 0 || N == 0 || (!msg_hop_hist && !node_received && !node_hop_sum)) return GSX_OK;
     const size_t cells = m * gsx::PROP_STATS_HOPS;
-    // device memory is written in place, in stream order; host memory gets a copy of the engine's buffers
-    const bool hist_dev = msg_hop_hist && on_device(msg_hop_hist);
-    const bool recv_dev = node_received && on_device(node_received);
-    const bool sum_dev = node_hop_sum && on_device(node_hop_sum);
-    if (!hist_dev && P.st_hist_cap < cells) {  // (the kernel always counts the histogram)
-        if (P.st_hist) {
-            HIPCHK(e, hipStreamSynchronize(e->stream));
-            (void)hipFree(P.st_hist);
-        }
-        P.st_hist = nullptr;
-        P.st_hist_cap = 0;
-        if (int rc = dalloc(e, &P.st_hist, cells)) return rc;
-        P.st_hist_cap = cells;
-    }
-    if (node_received && !recv_dev && !P.st_recv)
-        if (int rc = dalloc(e, &P.st_recv, N)) return rc;
-    if (node_hop_sum && !sum_dev && !P.st_sum)
-        if (int rc = dalloc(e, &P.st_sum, N)) return rc;
-    uint32_t* d_hist = hist_dev ? msg_hop_hist : P.st_hist;
-    uint32_t* d_recv = !node_received ? nullptr : recv_dev ? node_received : P.st_recv;
-    unsigned long long* d_sum =
-        !node_hop_sum ? nullptr : sum_dev ? reinterpret_cast<unsigned long long*>(node_hop_sum) : P.st_sum;
-    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
-    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
-    HIPCHK(e, hipMemsetAsync(d_hist, 0, 4 * cells, e->stream));
-    if (d_recv) HIPCHK(e, hipMemsetAsync(d_recv, 0, 4 * N, e->stream));
-    if (d_sum) HIPCHK(e, hipMemsetAsync(d_sum, 0, 8 * N, e->stream));
+    OutBinder B(e);
+    uint32_t* d_hist = B.bind(msg_hop_hist, P.st_hist, cells, true);
+    if (!d_hist) d_hist = B.scratch(P.st_hist, cells, true);  // (the kernel always counts the histogram)
+    uint32_t* const d_recv = B.bind(node_received, P.st_recv, N, true);
+    unsigned long long* const d_sum = B.bind(node_hop_sum, P.st_sum, N, true);
+    if (B.rc) return B.rc;
+    LaunchRegion reg(e);
+    HIPCHK(e, reg.begin());
+    if (int rc = B.zero()) return rc;
     HIPCHK(e, gsx::launch_prop_stats(ps, d_hist, d_recv, d_sum, e->stream));
-    if (region) {
-        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
-        ++e->t_used;
-    }
-    bool host = false;
-    if (msg_hop_hist && !hist_dev) {
-        HIPCHK(e, hipMemcpyAsync(msg_hop_hist, d_hist, 4 * cells, hipMemcpyDeviceToHost, e->stream));
-        host = true;
-    }
-    if (node_received && !recv_dev) {
-        HIPCHK(e, hipMemcpyAsync(node_received, d_recv, 4 * N, hipMemcpyDeviceToHost, e->stream));
-        host = true;
-    }
-    if (node_hop_sum && !sum_dev) {
-        HIPCHK(e, hipMemcpyAsync(node_hop_sum, d_sum, 8 * N, hipMemcpyDeviceToHost, e->stream));
-        host = true;
-    }
-    if (host) HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GSX_OK;
+    HIPCHK(e, reg.end());
+    return B.finish();
 }
-
-// One output of gsx_prop_traffic by gsx_prop_stats' pointer rules: device
-// memory is written in place, host memory gets a copy of an engine buffer
-// (grown on demand), NULL is skipped.
-extern "C++" {
-template <typename T>
-static int traffic_grow(gsx_engine* e, T** buf, size_t* cap, size_t n) {
-    if (*cap >= n) return GSX_OK;
-    if (*buf) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        (void)hipFree(*buf);
-    }
-    *buf = nullptr;
-    *cap = 0;
-    if (int rc = dalloc(e, buf, n)) return rc;
-    *cap = n;
-    return GSX_OK;
-}
-template <typename T>
-static int traffic_out(gsx_engine* e, T* user, T** buf, size_t* cap, size_t n, T** dev) {
-    *dev = nullptr;
-    if (!user) return GSX_OK;
-    if (on_device(user)) {
-        *dev = user;
-        return GSX_OK;
-    }
-    if (int rc = traffic_grow(e, buf, cap, n)) return rc;
-    *dev = *buf;
-    return GSX_OK;
-}
-}  // extern "C++"
 
 int gsx_prop_traffic(gsx_engine* e, const uint32_t* msg_bytes, uint32_t* msg_copies, uint32_t* node_copies,
                      uint64_t* node_bytes, uint32_t* pair_copies, uint64_t* pair_bytes) {
@@ -4413,19 +4438,16 @@ int gsx_prop_traffic(gsx_engine* e, const uint32_t* msg_bytes, uint32_t* msg_cop
     if (m == 0 || E == 0 || N == 0) return GSX_OK;
     if (!msg_copies && !node_copies && !node_bytes && !pair_copies && !pair_bytes) return GSX_OK;
     gsx::TrafficArgs a{};
-    unsigned long long *d_nb = nullptr, *d_pb = nullptr;
-    if (int rc = traffic_out(e, msg_copies, &P.tr_msg, &P.tr_msg_cap, m * gsx::TRAFFIC_COLS, &a.msg_copies)) return rc;
-    if (int rc = traffic_out(e, node_copies, &P.tr_node, &P.tr_node_cap, N * gsx::TRAFFIC_COLS, &a.node_copies)) return rc;
-    if (int rc = traffic_out(e, reinterpret_cast<unsigned long long*>(node_bytes), &P.tr_nbytes, &P.tr_nbytes_cap, 2 * N, &d_nb))
-        return rc;
-    if (int rc = traffic_out(e, pair_copies, &P.tr_pair, &P.tr_pair_cap, E, &a.pair_copies)) return rc;
-    if (int rc = traffic_out(e, reinterpret_cast<unsigned long long*>(pair_bytes), &P.tr_pbytes, &P.tr_pbytes_cap, E, &d_pb))
-        return rc;
-    a.node_bytes = d_nb;
-    a.pair_bytes = d_pb;
+    OutBinder B(e);
+    a.msg_copies = B.bind(msg_copies, P.tr_msg, m * gsx::TRAFFIC_COLS, false);
+    a.node_copies = B.bind(node_copies, P.tr_node, N * gsx::TRAFFIC_COLS, false);
+    a.node_bytes = B.bind(node_bytes, P.tr_nbytes, 2 * N, false);
+    a.pair_copies = B.bind(pair_copies, P.tr_pair, E, false);
+    a.pair_bytes = B.bind(pair_bytes, P.tr_pbytes, E, false);
+    if (B.rc) return B.rc;
     // the scratch rows, kept with the engine (dropped with the overlay)
-    if (int rc = traffic_grow(e, &P.tr_sset, &P.tr_sset_cap, N * W)) return rc;
-    a.sset = P.tr_sset;
+    if (int rc = P.tr_sset.reserve(e, N * W)) return rc;
+    a.sset = P.tr_sset.p;
     if (msg_bytes && (a.node_bytes || a.pair_bytes)) {
         // bit planes of the sizes, only up to the highest bit used: [plane][word] (at least one word, so
         // that sizes of all 0 are not taken for "no sizes")
@@ -4439,35 +4461,19 @@ int gsx_prop_traffic(gsx_engine* e, const uint32_t* msg_bytes, uint32_t* msg_cop
         for (size_t k = 0; k < m; ++k)
             for (uint32_t b = msg_bytes[k], j = 0; b; b >>= 1, ++j)
                 if (b & 1) P.tr_hplanes[(size_t)j * W + k / 64] |= 1ull << (k % 64);
-        if (int rc = traffic_grow(e, &P.tr_planes, &P.tr_planes_cap, P.tr_hplanes.size())) return rc;
-        HIPCHK(e, hipMemcpyAsync(P.tr_planes, P.tr_hplanes.data(), 8 * P.tr_hplanes.size(), hipMemcpyHostToDevice,
+        if (int rc = P.tr_planes.reserve(e, P.tr_hplanes.size())) return rc;
+        HIPCHK(e, hipMemcpyAsync(P.tr_planes.p, P.tr_hplanes.data(), 8 * P.tr_hplanes.size(), hipMemcpyHostToDevice,
                                  e->stream));
         P.tr_planes_busy = true;
-        a.planes = P.tr_planes;
+        a.planes = P.tr_planes.p;
         a.n_planes = np;
     }
-    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
-    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    LaunchRegion reg(e);
+    HIPCHK(e, reg.begin());
     HIPCHK(e, gsx::launch_prop_traffic(ps, a, e->stream));
-    if (region) {
-        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
-        ++e->t_used;
-    }
-    bool host = false;
-    auto back = [&](void* user, const void* dev, size_t bytes) -> hipError_t {
-        if (!user || user == dev) return hipSuccess;
-        host = true;
-        return hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, e->stream);
-    };
-    HIPCHK(e, back(msg_copies, a.msg_copies, 4 * m * gsx::TRAFFIC_COLS));
-    HIPCHK(e, back(node_copies, a.node_copies, 4 * N * gsx::TRAFFIC_COLS));
-    HIPCHK(e, back(node_bytes, a.node_bytes, 8 * 2 * N));
-    HIPCHK(e, back(pair_copies, a.pair_copies, 4 * E));
-    HIPCHK(e, back(pair_bytes, a.pair_bytes, 8 * E));
-    if (host) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        P.tr_planes_busy = false;
-    }
+    HIPCHK(e, reg.end());
+    if (int rc = B.finish()) return rc;
+    if (B.synced) P.tr_planes_busy = false;
     return GSX_OK;
 }
 
@@ -4747,53 +4753,17 @@ int gsx_timed_stats(gsx_engine* e, uint32_t bin_ticks, uint32_t n_bins, uint32_t
     const size_t m = ps.n_msgs, N = ps.n_nodes;
     if (m == 0 || N == 0 || (!msg_tick_hist && !node_received && !node_tick_sum)) return GSX_OK;
     const size_t cells = m * n_bins;
-    // device memory is written in place, in stream order; host memory gets a copy of the engine's buffers
-    const bool hist_dev = msg_tick_hist && on_device(msg_tick_hist);
-    const bool recv_dev = node_received && on_device(node_received);
-    const bool sum_dev = node_tick_sum && on_device(node_tick_sum);
-    if (msg_tick_hist && !hist_dev && T.st_hist_cap < cells) {
-        if (T.st_hist) {
-            HIPCHK(e, hipStreamSynchronize(e->stream));
-            (void)hipFree(T.st_hist);
-        }
-        T.st_hist = nullptr;
-        T.st_hist_cap = 0;
-        if (int rc = dalloc(e, &T.st_hist, cells)) return rc;
-        T.st_hist_cap = cells;
-    }
-    if (node_received && !recv_dev && !T.st_recv)
-        if (int rc = dalloc(e, &T.st_recv, N)) return rc;
-    if (node_tick_sum && !sum_dev && !T.st_sum)
-        if (int rc = dalloc(e, &T.st_sum, N)) return rc;
-    uint32_t* d_hist = !msg_tick_hist ? nullptr : hist_dev ? msg_tick_hist : T.st_hist;
-    uint32_t* d_recv = !node_received ? nullptr : recv_dev ? node_received : T.st_recv;
-    unsigned long long* d_sum =
-        !node_tick_sum ? nullptr : sum_dev ? reinterpret_cast<unsigned long long*>(node_tick_sum) : T.st_sum;
-    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
-    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
-    if (d_hist) HIPCHK(e, hipMemsetAsync(d_hist, 0, 4 * cells, e->stream));
-    if (d_recv) HIPCHK(e, hipMemsetAsync(d_recv, 0, 4 * N, e->stream));
-    if (d_sum) HIPCHK(e, hipMemsetAsync(d_sum, 0, 8 * N, e->stream));
+    OutBinder B(e);
+    uint32_t* const d_hist = B.bind(msg_tick_hist, T.st_hist, cells, true);
+    uint32_t* const d_recv = B.bind(node_received, T.st_recv, N, true);
+    unsigned long long* const d_sum = B.bind(node_tick_sum, T.st_sum, N, true);
+    if (B.rc) return B.rc;
+    LaunchRegion reg(e);
+    HIPCHK(e, reg.begin());
+    if (int rc = B.zero()) return rc;
     HIPCHK(e, gsx::launch_timed_stats(ps, T.ts, bin_ticks, n_bins, d_hist, d_recv, d_sum, e->stream));
-    if (region) {
-        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
-        ++e->t_used;
-    }
-    bool host = false;
-    if (msg_tick_hist && !hist_dev) {
-        HIPCHK(e, hipMemcpyAsync(msg_tick_hist, d_hist, 4 * cells, hipMemcpyDeviceToHost, e->stream));
-        host = true;
-    }
-    if (node_received && !recv_dev) {
-        HIPCHK(e, hipMemcpyAsync(node_received, d_recv, 4 * N, hipMemcpyDeviceToHost, e->stream));
-        host = true;
-    }
-    if (node_tick_sum && !sum_dev) {
-        HIPCHK(e, hipMemcpyAsync(node_tick_sum, d_sum, 8 * N, hipMemcpyDeviceToHost, e->stream));
-        host = true;
-    }
-    if (host) HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GSX_OK;
+    HIPCHK(e, reg.end());
+    return B.finish();
 }
 
 int gsx_timed_traffic(gsx_engine* e, const uint32_t* msg_bytes, uint32_t bin_ticks, uint32_t n_bins,
@@ -4820,58 +4790,36 @@ int gsx_timed_traffic(gsx_engine* e, const uint32_t* msg_bytes, uint32_t bin_tic
     if (!out->msg_copies && !out->node_copies && !out->node_bytes && !out->pair_copies && !out->pair_bytes &&
         !out->bin_copies && !out->bin_bytes && !out->node_peak && !out->node_peak_bin)
         return GSX_OK;
-    typedef unsigned long long ull;
     gsx::TimedTrafficArgs a{};
     a.bin_ticks = bin_ticks;
     a.n_bins = n_bins;
     const size_t K = gsx::TT_COLS;
-    int rc = 0;
-    if ((rc = traffic_out(e, out->msg_copies, &T.tt_msg, &T.tt_msg_cap, m * K, &a.msg_copies)) ||
-        (rc = traffic_out(e, out->node_copies, &T.tt_node, &T.tt_node_cap, N * K, &a.node_copies)) ||
-        (rc = traffic_out(e, reinterpret_cast<ull*>(out->node_bytes), &T.tt_nbytes, &T.tt_nbytes_cap, 2 * N, &a.node_bytes)) ||
-        (rc = traffic_out(e, out->pair_copies, &T.tt_pair, &T.tt_pair_cap, E, &a.pair_copies)) ||
-        (rc = traffic_out(e, reinterpret_cast<ull*>(out->pair_bytes), &T.tt_pbytes, &T.tt_pbytes_cap, E, &a.pair_bytes)) ||
-        (rc = traffic_out(e, reinterpret_cast<ull*>(out->bin_copies), &T.tt_bins, &T.tt_bins_cap, n_bins * K, &a.bin_copies)) ||
-        (rc = traffic_out(e, reinterpret_cast<ull*>(out->bin_bytes), &T.tt_bbytes, &T.tt_bbytes_cap, 2 * (size_t)n_bins,
-                          &a.bin_bytes)) ||
-        (rc = traffic_out(e, reinterpret_cast<ull*>(out->node_peak), &T.tt_peak, &T.tt_peak_cap, 2 * N, &a.node_peak)) ||
-        (rc = traffic_out(e, out->node_peak_bin, &T.tt_pkbin, &T.tt_pkbin_cap, 2 * N, &a.node_peak_bin)))
-        return rc;
+    OutBinder B(e);
+    a.msg_copies = B.bind(out->msg_copies, T.tt_msg, m * K, false);
+    a.node_copies = B.bind(out->node_copies, T.tt_node, N * K, false);
+    a.node_bytes = B.bind(out->node_bytes, T.tt_nbytes, 2 * N, false);
+    a.pair_copies = B.bind(out->pair_copies, T.tt_pair, E, false);
+    a.pair_bytes = B.bind(out->pair_bytes, T.tt_pbytes, E, false);
+    a.bin_copies = B.bind(out->bin_copies, T.tt_bins, n_bins * K, false);
+    a.bin_bytes = B.bind(out->bin_bytes, T.tt_bbytes, 2 * (size_t)n_bins, false);
+    a.node_peak = B.bind(out->node_peak, T.tt_peak, 2 * N, false);
+    a.node_peak_bin = B.bind(out->node_peak_bin, T.tt_pkbin, 2 * N, false);
+    if (B.rc) return B.rc;
     if (msg_bytes) {
         if (T.tt_sizes_busy) HIPCHK(e, hipStreamSynchronize(e->stream));  // (the last upload may still read them)
         T.tt_sizes_busy = false;
         T.tt_hsizes.assign(msg_bytes, msg_bytes + m);
-        if ((rc = traffic_grow(e, &T.tt_sizes, &T.tt_sizes_cap, m))) return rc;
-        HIPCHK(e, hipMemcpyAsync(T.tt_sizes, T.tt_hsizes.data(), 4 * m, hipMemcpyHostToDevice, e->stream));
+        if (int rc = T.tt_sizes.reserve(e, m)) return rc;
+        HIPCHK(e, hipMemcpyAsync(T.tt_sizes.p, T.tt_hsizes.data(), 4 * m, hipMemcpyHostToDevice, e->stream));
         T.tt_sizes_busy = true;
-        a.sizes = T.tt_sizes;
+        a.sizes = T.tt_sizes.p;
     }
-    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
-    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    LaunchRegion reg(e);
+    HIPCHK(e, reg.begin());
     HIPCHK(e, gsx::launch_timed_traffic(ps, T.ts, a, e->stream));
-    if (region) {
-        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
-        ++e->t_used;
-    }
-    bool host = false;
-    auto back = [&](void* user, const void* dev, size_t bytes) -> hipError_t {
-        if (!user || user == dev) return hipSuccess;
-        host = true;
-        return hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, e->stream);
-    };
-    HIPCHK(e, back(out->msg_copies, a.msg_copies, 4 * m * K));
-    HIPCHK(e, back(out->node_copies, a.node_copies, 4 * N * K));
-    HIPCHK(e, back(out->node_bytes, a.node_bytes, 8 * 2 * N));
-    HIPCHK(e, back(out->pair_copies, a.pair_copies, 4 * E));
-    HIPCHK(e, back(out->pair_bytes, a.pair_bytes, 8 * E));
-    HIPCHK(e, back(out->bin_copies, a.bin_copies, 8 * n_bins * K));
-    HIPCHK(e, back(out->bin_bytes, a.bin_bytes, 8 * 2 * (size_t)n_bins));
-    HIPCHK(e, back(out->node_peak, a.node_peak, 8 * 2 * N));
-    HIPCHK(e, back(out->node_peak_bin, a.node_peak_bin, 4 * 2 * N));
-    if (host) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        T.tt_sizes_busy = false;
-    }
+    HIPCHK(e, reg.end());
+    if (int rc = B.finish()) return rc;
+    if (B.synced) T.tt_sizes_busy = false;
     return GSX_OK;
 }
 
@@ -4890,17 +4838,25 @@ int gsx_score_stats_edges(gsx_engine* e, gsx_score_stats_spec* spec) {
     return GSX_OK;
 }
 
-int gsx_score_stats(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_score_stats_out* out) {
-    static_assert(gsx::SS_MAX_EDGES == GSX_SS_MAX_EDGES && gsx::SS_PRESENT == GSX_SS_PRESENT &&
-                      gsx::SS_CONNECTED == GSX_SS_CONNECTED && gsx::SS_MESH == GSX_SS_MESH,
-                  "the kernel's constants are the header's");
-    if (!e || !spec || !out) return GSX_EINVAL;
+namespace {
+// The spec of gsx_score_stats and gsx_score_parts.
+int score_spec_check(gsx_engine* e, const gsx_score_stats_spec* spec) {
     if (spec->select > GSX_SS_MESH) return fail(e, GSX_EINVAL, "unknown selection");
     if (spec->n_edges > GSX_SS_MAX_EDGES) return fail(e, GSX_EINVAL, "more than GSX_SS_MAX_EDGES edges");
     for (uint32_t k = 0; k < spec->n_edges; ++k)
         if (invalid_number(spec->edges[k]) || (k && !(spec->edges[k] > spec->edges[k - 1])))
             return fail(e, GSX_EINVAL, "edges must be finite and strictly ascending");
     if (spec->select == GSX_SS_MESH && spec->topic >= e->T) return fail(e, GSX_EINVAL, "topic out of range");
+    return GSX_OK;
+}
+}  // namespace
+
+int gsx_score_stats(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_score_stats_out* out) {
+    static_assert(gsx::SS_MAX_EDGES == GSX_SS_MAX_EDGES && gsx::SS_PRESENT == GSX_SS_PRESENT &&
+                      gsx::SS_CONNECTED == GSX_SS_CONNECTED && gsx::SS_MESH == GSX_SS_MESH,
+                  "the kernel's constants are the header's");
+    if (!e || !spec || !out) return GSX_EINVAL;
+    if (int rc = score_spec_check(e, spec)) return rc;
     if (int rc = gx_busy(e)) return rc;
     if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
     if (!out->hist && !out->obs_bins && !out->obs_min && !out->peer_bins && !out->peer_min) return GSX_OK;
@@ -4908,26 +4864,14 @@ int gsx_score_stats(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_s
     if (int rc = ensure_scores(e)) return rc;
     auto& P = e->prop;
     const size_t nb = (size_t)spec->n_edges + 1, NL = e->n_nodes, NT = e->n_total;
-    // device memory is written in place, in stream order; host memory gets a copy of the engine's buffers
-    const bool h_hist = out->hist && !on_device(out->hist), h_ob = out->obs_bins && !on_device(out->obs_bins),
-               h_om = out->obs_min && !on_device(out->obs_min), h_pb = out->peer_bins && !on_device(out->peer_bins),
-               h_pm = out->peer_min && !on_device(out->peer_min);
-    if (h_hist && !P.ss_hist)
-        if (int rc = dalloc(e, &P.ss_hist, gsx::SS_MAX_BINS)) return rc;
-    if (h_ob && !P.ss_obs_bins)
-        if (int rc = dalloc(e, &P.ss_obs_bins, NL * gsx::SS_MAX_BINS)) return rc;
-    if (h_om && !P.ss_obs_min)
-        if (int rc = dalloc(e, &P.ss_obs_min, NL)) return rc;
-    if (h_pb && !P.ss_peer_bins)
-        if (int rc = dalloc(e, &P.ss_peer_bins, NT * gsx::SS_MAX_BINS)) return rc;
-    if (h_pm && !P.ss_peer_min)
-        if (int rc = dalloc(e, &P.ss_peer_min, NT)) return rc;
-    using u64p = unsigned long long*;
-    const u64p d_hist = h_hist ? P.ss_hist : reinterpret_cast<u64p>(out->hist);
-    uint32_t* const d_ob = h_ob ? P.ss_obs_bins : out->obs_bins;
-    const u64p d_om = h_om ? P.ss_obs_min : reinterpret_cast<u64p>(out->obs_min);
-    uint32_t* const d_pb = h_pb ? P.ss_peer_bins : out->peer_bins;
-    const u64p d_pm = h_pm ? P.ss_peer_min : reinterpret_cast<u64p>(out->peer_min);
+    constexpr size_t MAXB = gsx::SS_MAX_BINS;  // (the room of every table: more edges later fit)
+    OutBinder B(e);
+    unsigned long long* const d_hist = B.bind(out->hist, P.ss_hist, nb, true, MAXB);
+    uint32_t* const d_ob = B.bind(out->obs_bins, P.ss_obs_bins, NL * nb, true, NL * MAXB);
+    unsigned long long* const d_om = B.bind(out->obs_min, P.ss_obs_min, NL, false);  // (launch_score_stats_fill's)
+    uint32_t* const d_pb = B.bind(out->peer_bins, P.ss_peer_bins, NT * nb, true, NT * MAXB);
+    unsigned long long* const d_pm = B.bind(out->peer_min, P.ss_peer_min, NT, false);
+    if (B.rc) return B.rc;
     gsx::ScoreStatsArgs a{};
     a.score = e->d_score;
     a.pflags = e->d_pflags;
@@ -4945,25 +4889,14 @@ int gsx_score_stats(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_s
     a.obs_min = d_om;
     a.peer_bins = d_pb;
     a.peer_min = d_pm;
-    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
-    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
-    if (d_hist) HIPCHK(e, hipMemsetAsync(d_hist, 0, 8 * nb, e->stream));
-    if (d_ob) HIPCHK(e, hipMemsetAsync(d_ob, 0, 4 * NL * nb, e->stream));
-    if (d_pb) HIPCHK(e, hipMemsetAsync(d_pb, 0, 4 * NT * nb, e->stream));
+    LaunchRegion reg(e);
+    HIPCHK(e, reg.begin());
+    if (int rc = B.zero()) return rc;
     HIPCHK(e, gsx::launch_score_stats_fill(d_om, NL, d_pm, NT, e->stream));
     HIPCHK(e, gsx::launch_score_stats(a, e->stream));
     HIPCHK(e, gsx::launch_score_stats_unkey(d_om, NL, d_pm, NT, e->stream));
-    if (region) {
-        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
-        ++e->t_used;
-    }
-    if (h_hist) HIPCHK(e, hipMemcpyAsync(out->hist, d_hist, 8 * nb, hipMemcpyDeviceToHost, e->stream));
-    if (h_ob) HIPCHK(e, hipMemcpyAsync(out->obs_bins, d_ob, 4 * NL * nb, hipMemcpyDeviceToHost, e->stream));
-    if (h_om) HIPCHK(e, hipMemcpyAsync(out->obs_min, d_om, 8 * NL, hipMemcpyDeviceToHost, e->stream));
-    if (h_pb) HIPCHK(e, hipMemcpyAsync(out->peer_bins, d_pb, 4 * NT * nb, hipMemcpyDeviceToHost, e->stream));
-    if (h_pm) HIPCHK(e, hipMemcpyAsync(out->peer_min, d_pm, 8 * NT, hipMemcpyDeviceToHost, e->stream));
-    if (h_hist || h_ob || h_om || h_pb || h_pm) HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GSX_OK;
+    HIPCHK(e, reg.end());
+    return B.finish();
 }
 
 int gsx_score_parts(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_score_parts_out* out) {
@@ -4975,12 +4908,7 @@ int gsx_score_parts(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_s
                       gsx::SP_SCORE == GSX_PART_SCORE,
                   "the kernel's constants are the header's");
     if (!e || !spec || !out) return GSX_EINVAL;
-    if (spec->select > GSX_SS_MESH) return fail(e, GSX_EINVAL, "unknown selection");
-    if (spec->n_edges > GSX_SS_MAX_EDGES) return fail(e, GSX_EINVAL, "more than GSX_SS_MAX_EDGES edges");
-    for (uint32_t k = 0; k < spec->n_edges; ++k)
-        if (invalid_number(spec->edges[k]) || (k && !(spec->edges[k] > spec->edges[k - 1])))
-            return fail(e, GSX_EINVAL, "edges must be finite and strictly ascending");
-    if (spec->select == GSX_SS_MESH && spec->topic >= e->T) return fail(e, GSX_EINVAL, "topic out of range");
+    if (int rc = score_spec_check(e, spec)) return rc;
     if (int rc = gx_busy(e)) return rc;  // (before the shard test: only a range shard can have one in flight)
     if (e->sharded()) return fail(e, GSX_EINVAL, "gsx_score_parts is not offered on a range shard");
     if (!e->loaded) return fail(e, GSX_ESTATE, "no overlay loaded");
@@ -4992,38 +4920,10 @@ int gsx_score_parts(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_s
     auto& P = e->prop;
     const size_t nb = (size_t)spec->n_edges + 1, NL = e->n_nodes, NT = e->n_total, E = e->E, ntc = (size_t)e->T + 1;
     constexpr size_t NC = GSX_CAUSES, MAXB = gsx::SS_MAX_BINS;
-    // device memory is written in place, in stream order; host memory gets a copy of the engine's
-    // buffers (the tables) or of a buffer of this call (the pair outputs)
-    const bool h_pp = out->pair_parts && E && !on_device(out->pair_parts),
-               h_pc = out->pair_cause && E && !on_device(out->pair_cause),
-               h_pt = out->pair_topic && E && !on_device(out->pair_topic),
-               h_ch = out->cause_hist && !on_device(out->cause_hist),
-               h_th = out->topic_hist && !on_device(out->topic_hist),
-               h_oc = out->obs_cause && NL && !on_device(out->obs_cause),
-               h_pe = out->peer_cause && NT && !on_device(out->peer_cause);
-    if (h_ch && !P.sp_cause_hist)
-        if (int rc = dalloc(e, &P.sp_cause_hist, MAXB * NC)) return rc;
-    if (h_th && !P.sp_topic_hist)
-        if (int rc = dalloc(e, &P.sp_topic_hist, MAXB * (GSX_MAX_TOPICS + 1))) return rc;
-    if (h_oc && !P.sp_obs_cause)
-        if (int rc = dalloc(e, &P.sp_obs_cause, NL * NC)) return rc;
-    if (h_pe && !P.sp_peer_cause)
-        if (int rc = dalloc(e, &P.sp_peer_cause, NT * NC)) return rc;
-    double* t_pp = nullptr;
-    uint8_t *t_pc = nullptr, *t_pt = nullptr;
-    auto drop = [&]() {
-        for (void* p : {(void*)t_pp, (void*)t_pc, (void*)t_pt})
-            if (p) (void)hipFree(p);
-    };
-    int rc = GSX_OK;
-    if (h_pp) rc = dalloc(e, &t_pp, E * GSX_PARTS);
-    if (!rc && h_pc) rc = dalloc(e, &t_pc, E);
-    if (!rc && h_pt) rc = dalloc(e, &t_pt, E);
-    if (rc) {
-        drop();
-        return rc;
-    }
-    using u64p = unsigned long long*;
+    // The tables are staged in the engine's buffers; the three pair outputs in buffers of
+    // this call, freed on return (80 B per pair do not stay resident).
+    StageBuf<double> t_pp;
+    StageBuf<uint8_t> t_pc, t_pt;
     gsx::ScorePartsArgs a{};
     a.pair_obs = e->d_pair_obs;
     a.col = e->d_col;
@@ -5031,39 +4931,26 @@ int gsx_score_parts(gsx_engine* e, const gsx_score_stats_spec* spec, const gsx_s
     a.topic = spec->select == GSX_SS_MESH ? spec->topic : 0;
     a.n_edges = spec->n_edges;
     for (uint32_t k = 0; k < spec->n_edges; ++k) a.edges[k] = spec->edges[k];
-    a.pair_parts = !E ? nullptr : h_pp ? t_pp : out->pair_parts;
-    a.pair_cause = !E ? nullptr : h_pc ? t_pc : out->pair_cause;
-    a.pair_topic = !E ? nullptr : h_pt ? t_pt : out->pair_topic;
-    a.cause_hist = h_ch ? P.sp_cause_hist : reinterpret_cast<u64p>(out->cause_hist);
-    a.topic_hist = h_th ? P.sp_topic_hist : reinterpret_cast<u64p>(out->topic_hist);
-    a.obs_cause = !NL ? nullptr : h_oc ? P.sp_obs_cause : out->obs_cause;
-    a.peer_cause = !NT ? nullptr : h_pe ? P.sp_peer_cause : out->peer_cause;
-    // (a failed call below leaves the stream's work to finish before the pair buffers go)
+    OutBinder B(e);
+    a.pair_parts = B.bind(out->pair_parts, t_pp, E * GSX_PARTS, false);
+    a.pair_cause = B.bind(out->pair_cause, t_pc, E, false);
+    a.pair_topic = B.bind(out->pair_topic, t_pt, E, false);
+    a.cause_hist = B.bind(out->cause_hist, P.sp_cause_hist, nb * NC, true, MAXB * NC);
+    a.topic_hist = B.bind(out->topic_hist, P.sp_topic_hist, nb * ntc, true, MAXB * (GSX_MAX_TOPICS + 1));
+    a.obs_cause = B.bind(out->obs_cause, P.sp_obs_cause, NL * NC, true);
+    a.peer_cause = B.bind(out->peer_cause, P.sp_peer_cause, NT * NC, true);
+    if (B.rc) return B.rc;
     auto run = [&]() -> int {
-        const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
-        if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
-        if (a.cause_hist) HIPCHK(e, hipMemsetAsync(a.cause_hist, 0, 8 * nb * NC, e->stream));
-        if (a.topic_hist) HIPCHK(e, hipMemsetAsync(a.topic_hist, 0, 8 * nb * ntc, e->stream));
-        if (a.obs_cause) HIPCHK(e, hipMemsetAsync(a.obs_cause, 0, 4 * NL * NC, e->stream));
-        if (a.peer_cause) HIPCHK(e, hipMemsetAsync(a.peer_cause, 0, 4 * NT * NC, e->stream));
+        LaunchRegion reg(e);
+        HIPCHK(e, reg.begin());
+        if (int rc = B.zero()) return rc;
         HIPCHK(e, gsx::launch_score_parts(dev_state(e), kern_params(e), a, e->stream));
-        if (region) {
-            HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
-            ++e->t_used;
-        }
-        if (h_pp) HIPCHK(e, hipMemcpyAsync(out->pair_parts, t_pp, 8 * E * GSX_PARTS, hipMemcpyDeviceToHost, e->stream));
-        if (h_pc) HIPCHK(e, hipMemcpyAsync(out->pair_cause, t_pc, E, hipMemcpyDeviceToHost, e->stream));
-        if (h_pt) HIPCHK(e, hipMemcpyAsync(out->pair_topic, t_pt, E, hipMemcpyDeviceToHost, e->stream));
-        if (h_ch) HIPCHK(e, hipMemcpyAsync(out->cause_hist, a.cause_hist, 8 * nb * NC, hipMemcpyDeviceToHost, e->stream));
-        if (h_th) HIPCHK(e, hipMemcpyAsync(out->topic_hist, a.topic_hist, 8 * nb * ntc, hipMemcpyDeviceToHost, e->stream));
-        if (h_oc) HIPCHK(e, hipMemcpyAsync(out->obs_cause, a.obs_cause, 4 * NL * NC, hipMemcpyDeviceToHost, e->stream));
-        if (h_pe) HIPCHK(e, hipMemcpyAsync(out->peer_cause, a.peer_cause, 4 * NT * NC, hipMemcpyDeviceToHost, e->stream));
-        if (h_pp || h_pc || h_pt || h_ch || h_th || h_oc || h_pe) HIPCHK(e, hipStreamSynchronize(e->stream));
-        return GSX_OK;
+        HIPCHK(e, reg.end());
+        return B.finish();
     };
-    rc = run();
-    if (rc && (t_pp || t_pc || t_pt)) (void)hipStreamSynchronize(e->stream);
-    drop();
+    const int rc = run();
+    // (a failed call leaves the stream's work to finish before the pair buffers go)
+    if (rc && (t_pp.p || t_pc.p || t_pt.p)) (void)hipStreamSynchronize(e->stream);
     return rc;
 }
 
@@ -5117,11 +5004,10 @@ int gsx_mesh_stats(gsx_engine* e, const gsx_mesh_stats_spec* spec, const gsx_mes
         if (dev) {
             d_class = spec->node_class;
         } else {
-            if (!P.ms_class)
-                if (int rc = dalloc(e, &P.ms_class, N)) return rc;
-            HIPCHK(e, hipMemcpyAsync(P.ms_class, P.ms_hclass.data(), N, hipMemcpyHostToDevice, e->stream));
+            if (int rc = P.ms_class.reserve(e, N)) return rc;
+            HIPCHK(e, hipMemcpyAsync(P.ms_class.p, P.ms_hclass.data(), N, hipMemcpyHostToDevice, e->stream));
             P.ms_class_busy = true;
-            d_class = P.ms_class;
+            d_class = P.ms_class.p;
         }
     }
     // NEGATIVE reads the score vector as gsx_score_stats does; the other columns the settled flags
@@ -5133,51 +5019,31 @@ int gsx_mesh_stats(gsx_engine* e, const gsx_mesh_stats_spec* spec, const gsx_mes
             if (int rc = flush(e)) return rc;
         }
     }
-    // sizes (elements) of the ten outputs; the first six are u64 tables, the others u32 node tables
+    // sizes (elements) of the six u64 tables; the four u32 node tables that follow have TN, TN, TN, TN * C
     const size_t nb = spec->n_bins, nab = (size_t)spec->n_age_edges + 1;
-    const size_t len[10] = {T * GSX_MS_COLS, T * nb, T * nb, T * nb, T * nab, T * C * C, TN, TN, TN, TN * C};
+    const size_t len[6] = {T * GSX_MS_COLS, T * nb, T * nb, T * nb, T * nab, T * C * C};
+    // (the room of a staged table: no later call's bins, edges or classes outgrow it)
     constexpr size_t MAXT = GSX_MAX_TOPICS;
-    const size_t tab_off[7] = {0,
-                               MAXT * GSX_MS_COLS,
-                               MAXT * (GSX_MS_COLS + GSX_MS_MAX_BINS),
-                               MAXT * (GSX_MS_COLS + 2 * GSX_MS_MAX_BINS),
-                               MAXT * (GSX_MS_COLS + 3 * GSX_MS_MAX_BINS),
-                               MAXT * (GSX_MS_COLS + 3 * GSX_MS_MAX_BINS + GSX_MS_MAX_AGE_EDGES + 1),
-                               MAXT * (GSX_MS_COLS + 3 * GSX_MS_MAX_BINS + GSX_MS_MAX_AGE_EDGES + 1 +
-                                       GSX_MS_MAX_CLASSES * GSX_MS_MAX_CLASSES)};
-    // device memory is written in place, in stream order; host memory gets a copy of the engine's buffers
-    bool host[10];
-    void* dev[10];
-    for (int k = 0; k < 10; ++k) {
-        host[k] = user[k] && len[k] && !on_device(user[k]);
-        dev[k] = host[k] || !len[k] ? nullptr : user[k];
-    }
+    const size_t room[6] = {MAXT * GSX_MS_COLS,      MAXT * GSX_MS_MAX_BINS,
+                            MAXT * GSX_MS_MAX_BINS,  MAXT * GSX_MS_MAX_BINS,
+                            MAXT * (GSX_MS_MAX_AGE_EDGES + 1), MAXT * GSX_MS_MAX_CLASSES * GSX_MS_MAX_CLASSES};
+    OutBinder B(e);
+    unsigned long long* tab[6];
+    for (int k = 0; k < 6; ++k) tab[k] = B.bind(static_cast<uint64_t*>(user[k]), P.ms_tab[k], len[k], true, room[k]);
     const bool units = out->topic_tot || out->deg_hist || out->out_hist || out->in_hist;  // pass 2 runs
-    // what pass 2 reads where the user gave no (device) table: degree, outbound, in-degree, honest degree
-    const bool need[4] = {out->topic_tot || out->deg_hist || host[6], out->topic_tot || out->out_hist || host[7],
-                          out->in_hist || host[8], out->topic_tot && d_class};
-    if (std::any_of(host, host + 6, [](bool b) { return b; }) && !P.ms_tab)
-        if (int rc = dalloc(e, &P.ms_tab, tab_off[6])) return rc;
-    for (int k = 0; k < 6; ++k)
-        if (host[k]) dev[k] = P.ms_tab + tab_off[k];
-    uint32_t* node[4] = {static_cast<uint32_t*>(dev[6]), static_cast<uint32_t*>(dev[7]), static_cast<uint32_t*>(dev[8]),
-                         nullptr};
-    for (int k = 0; k < 4; ++k)
-        if (!node[k] && need[k]) {
-            if (!P.ms_node[k])
-                if (int rc = dalloc(e, &P.ms_node[k], TN)) return rc;
-            node[k] = P.ms_node[k];
-        }
-    if (host[9]) {
-        if (!P.ms_ncd)
-            if (int rc = dalloc(e, &P.ms_ncd, TN * GSX_MS_MAX_CLASSES)) return rc;
-        dev[9] = P.ms_ncd;
+    // what pass 2 reads where the user asked for no such table: degree, outbound, in-degree, honest degree
+    const bool need[4] = {out->topic_tot || out->deg_hist, out->topic_tot || out->out_hist, out->in_hist != nullptr,
+                          out->topic_tot && d_class};
+    uint32_t* node[4];
+    for (int k = 0; k < 4; ++k) {
+        node[k] = k < 3 ? B.bind(static_cast<uint32_t*>(user[6 + k]), P.ms_node[k], TN, true) : nullptr;
+        if (!node[k] && need[k]) node[k] = B.scratch(P.ms_node[k], TN, true);
     }
+    uint32_t* const ncd = B.bind(out->node_class_deg, P.ms_ncd, TN * C, true, TN * GSX_MS_MAX_CLASSES);
     const bool fan = out->topic_tot && e->members_on;
-    if (fan && !P.ms_fan)
-        if (int rc = dalloc(e, &P.ms_fan, N)) return rc;
+    unsigned long long* const fan_any = fan ? B.scratch(P.ms_fan, N, true) : nullptr;
+    if (B.rc) return B.rc;
 
-    using u64p = unsigned long long*;
     gsx::MeshStatsArgs a{};
     a.pflags = e->d_pflags;
     a.eflags = e->d_eflags;
@@ -5205,44 +5071,27 @@ int gsx_mesh_stats(gsx_engine* e, const gsx_mesh_stats_spec* spec, const gsx_mes
     a.d_out = e->gp.d_out;
     a.now = spec->now_ns;
     for (uint32_t k = 0; k < spec->n_age_edges; ++k) a.age_edges[k] = spec->age_edges_ns[k];
-    a.tot = static_cast<u64p>(dev[0]);
-    a.deg_hist = static_cast<u64p>(dev[1]);
-    a.out_hist = static_cast<u64p>(dev[2]);
-    a.in_hist = static_cast<u64p>(dev[3]);
-    a.age_hist = static_cast<u64p>(dev[4]);
-    a.class_links = static_cast<u64p>(dev[5]);
+    a.tot = tab[0];
+    a.deg_hist = tab[1];
+    a.out_hist = tab[2];
+    a.in_hist = tab[3];
+    a.age_hist = tab[4];
+    a.class_links = tab[5];
     a.node_deg = node[0];
     a.node_out = node[1];
     a.node_in = node[2];
     a.node_honest = node[3];
-    a.node_class_deg = static_cast<uint32_t*>(dev[9]);
-    a.fan_any = fan ? P.ms_fan : nullptr;
+    a.node_class_deg = ncd;
+    a.fan_any = fan_any;
 
-    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
-    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
-    for (int k = 0; k < 6; ++k)
-        if (dev[k]) HIPCHK(e, hipMemsetAsync(dev[k], 0, 8 * len[k], e->stream));
-    for (int k = 0; k < 4; ++k)
-        if (node[k]) HIPCHK(e, hipMemsetAsync(node[k], 0, 4 * TN, e->stream));
-    if (dev[9]) HIPCHK(e, hipMemsetAsync(dev[9], 0, 4 * len[9], e->stream));
-    if (a.fan_any) HIPCHK(e, hipMemsetAsync(a.fan_any, 0, 8 * N, e->stream));
+    LaunchRegion reg(e);
+    HIPCHK(e, reg.begin());
+    if (int rc = B.zero()) return rc;
     HIPCHK(e, gsx::launch_mesh_pairs(a, e->stream));
     if (units) HIPCHK(e, gsx::launch_mesh_units(a, e->stream));
-    if (region) {
-        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
-        ++e->t_used;
-    }
-    bool any_host = false;
-    for (int k = 0; k < 10; ++k) {
-        if (!host[k]) continue;
-        const void* src = k < 6 ? dev[k] : k < 9 ? static_cast<void*>(node[k - 6]) : dev[9];
-        HIPCHK(e, hipMemcpyAsync(user[k], src, (k < 6 ? 8 : 4) * len[k], hipMemcpyDeviceToHost, e->stream));
-        any_host = true;
-    }
-    if (any_host) {
-        HIPCHK(e, hipStreamSynchronize(e->stream));
-        P.ms_class_busy = false;
-    }
+    HIPCHK(e, reg.end());
+    if (int rc = B.finish()) return rc;
+    if (B.synced) P.ms_class_busy = false;
     return GSX_OK;
 }
 
@@ -5433,40 +5282,29 @@ int gsx_accept_from(gsx_engine* e, const uint64_t* pairs, size_t n, int64_t now_
     a.draw = draw;
     a.gater = G.on ? 1u : 0u;
     if (pairs) {
-        if (G.list_cap < n) {
-            HIPCHK(e, hipStreamSynchronize(e->stream));
-            if (G.list_out) (void)hipFree(G.list_out);
-            if (G.list_pairs) (void)hipFree(G.list_pairs);
-            G.list_out = nullptr;
-            G.list_pairs = nullptr;
-            G.list_cap = 0;
-            const size_t want = std::max<size_t>(2 * n, 1024);
-            int rc = 0;
-            if ((rc = dalloc(e, &G.list_out, want)) || (rc = dalloc(e, &G.list_pairs, want))) return rc;
-            G.list_cap = want;
-        }
-        HIPCHK(e, hipMemcpyAsync(G.list_pairs, pairs, 8 * n, hipMemcpyHostToDevice, e->stream));
-        a.pairs = G.list_pairs;
-        a.out = host_out ? G.list_out : out;
+        // (both lists grow together, with headroom: listed calls come in many sizes)
+        const size_t want = G.list_pairs.cap < n ? std::max<size_t>(2 * n, 1024) : n;
+        int rc = 0;
+        if ((rc = G.list_out.reserve(e, want)) || (rc = G.list_pairs.reserve(e, want))) return rc;
+        HIPCHK(e, hipMemcpyAsync(G.list_pairs.p, pairs, 8 * n, hipMemcpyHostToDevice, e->stream));
+        a.pairs = G.list_pairs.p;
+        a.out = host_out ? G.list_out.p : out;
     } else {
         if (!G.decision)  // (an engine without a gater keeps its decision bytes too)
             if (int rc = dalloc(e, &G.decision, e->E)) return rc;
         a.out = G.decision;
     }
-    const bool region = e->t_active && e->t_used < e->t_max;  // gsx_timing_begin: this call is one timed launch
-    if (region) HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used], e->stream));
+    LaunchRegion reg(e);
+    HIPCHK(e, reg.begin());
     HIPCHK(e, gsx::launch_accept_from(dev_gater(e), a, e->stream));
-    if (region) {
-        HIPCHK(e, hipEventRecord(e->tev[2 * e->t_used + 1], e->stream));
-        ++e->t_used;
-    }
+    HIPCHK(e, reg.end());
     if (!pairs) {
         G.have_decision = true;
         G.counted = false;
         ++e->gater_dec_gen;
         HIPCHK(e, hipMemcpyAsync(out, G.decision, n, host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, e->stream));
     } else if (host_out) {
-        HIPCHK(e, hipMemcpyAsync(out, G.list_out, n, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(e, hipMemcpyAsync(out, G.list_out.p, n, hipMemcpyDeviceToHost, e->stream));
     }
     if (host_out || pairs) HIPCHK(e, hipStreamSynchronize(e->stream));  // (pairs: the list was the copy's source)
     return GSX_OK;
@@ -5614,20 +5452,6 @@ int tag_on(gsx_engine* e) {
 bool tag_joined(const gsx_engine* e, uint32_t u, uint32_t topic) {
     return !e->members_on || ((e->h_sub[u] >> topic) & 1);
 }
-
-// gsx_timing_begin: the call's launches are one timed region
-struct TagRegion {
-    gsx_engine* e;
-    bool on;
-    explicit TagRegion(gsx_engine* e_) : e(e_), on(e_->t_active && e_->t_used < e_->t_max) {}
-    hipError_t begin() { return on ? hipEventRecord(e->tev[2 * e->t_used], e->stream) : hipSuccess; }
-    hipError_t end() {
-        if (!on) return hipSuccess;
-        const hipError_t st = hipEventRecord(e->tev[2 * e->t_used + 1], e->stream);
-        ++e->t_used;
-        return st;
-    }
-};
 
 // The bumps of validated events: unjoined observers dropped, equal keys merged,
 // one launch.  Every step is a saturating add of a positive amount, so the
@@ -5784,7 +5608,7 @@ int gsx_tag_decay(gsx_engine* e, uint64_t steps) {
     if (int rc = gx_busy(e)) return rc;
     if (int rc = tag_on(e)) return rc;
     const uint64_t sub = std::min<uint64_t>(steps, 255) * e->tagt.p.decay_amount;  // (a tag is at most 255)
-    TagRegion reg(e);
+    LaunchRegion reg(e);
     HIPCHK(e, reg.begin());
     HIPCHK(e, gsx::launch_tag_decay(dev_tags(e), (uint32_t)std::min<uint64_t>(sub, 255), e->stream));
     HIPCHK(e, reg.end());
@@ -5825,7 +5649,7 @@ int gsx_tag_fold_prop(gsx_engine* e) {
     }
     uint64_t* const d_acc = G.fold_buf;
     uint64_t* const d_dup = G.fold_buf + W;
-    TagRegion reg(e);
+    LaunchRegion reg(e);
     hipError_t st = hipMemcpyAsync(d_acc, acc.data(), 8 * acc.size(), hipMemcpyHostToDevice, e->stream);
     if (st == hipSuccess) st = reg.begin();
     if (st == hipSuccess && near) st = gsx::launch_prop_dup_rows(ps, d_dup, e->stream);
@@ -5844,10 +5668,9 @@ int gsx_tag_export(gsx_engine* e, uint8_t* tags) {
     if (int rc = tag_on(e)) return rc;
     const size_t n = (size_t)e->E * e->T;
     if (n == 0) return GSX_OK;
-    if (!G.exp_buf)
-        if (int rc = dalloc(e, &G.exp_buf, n)) return rc;
-    HIPCHK(e, gsx::launch_tag_export(dev_tags(e), G.exp_buf, e->stream));
-    HIPCHK(e, hipMemcpyAsync(tags, G.exp_buf, n, hipMemcpyDeviceToHost, e->stream));
+    if (int rc = G.exp_buf.reserve(e, n)) return rc;
+    HIPCHK(e, gsx::launch_tag_export(dev_tags(e), G.exp_buf.p, e->stream));
+    HIPCHK(e, hipMemcpyAsync(tags, G.exp_buf.p, n, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return GSX_OK;
 }
@@ -5861,21 +5684,15 @@ int gsx_conn_values(gsx_engine* e, uint32_t* value, uint8_t* protect) {
     if (int rc = tag_on(e)) return rc;
     if ((!value && !protect) || e->E == 0) return GSX_OK;
     if (int rc = flush(e)) return rc;  // queued Graft / Prune / AddPeer events move the protection bits
-    const bool h_val = value && !on_device(value), h_prot = protect && !on_device(protect);
-    if (h_val && !G.val_buf)
-        if (int rc = dalloc(e, &G.val_buf, e->E)) return rc;
-    if (h_prot && !G.prot_buf)
-        if (int rc = dalloc(e, &G.prot_buf, e->E)) return rc;
-    uint32_t* const d_val = h_val ? G.val_buf : value;
-    uint8_t* const d_prot = h_prot ? G.prot_buf : protect;
-    TagRegion reg(e);
+    OutBinder B(e);
+    uint32_t* const d_val = B.bind(value, G.val_buf, e->E, false);
+    uint8_t* const d_prot = B.bind(protect, G.prot_buf, e->E, false);
+    if (B.rc) return B.rc;
+    LaunchRegion reg(e);
     HIPCHK(e, reg.begin());
     HIPCHK(e, gsx::launch_conn_values(dev_tags(e), d_val, d_prot, nullptr, e->stream));
     HIPCHK(e, reg.end());
-    if (h_val) HIPCHK(e, hipMemcpyAsync(value, d_val, 4 * e->E, hipMemcpyDeviceToHost, e->stream));
-    if (h_prot) HIPCHK(e, hipMemcpyAsync(protect, d_prot, e->E, hipMemcpyDeviceToHost, e->stream));
-    if (h_val || h_prot) HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GSX_OK;
+    return B.finish();
 }
 
 int gsx_conn_trim(gsx_engine* e, uint32_t low_water, uint8_t* trim, uint32_t* node_trimmed) {
@@ -5886,26 +5703,20 @@ int gsx_conn_trim(gsx_engine* e, uint32_t low_water, uint8_t* trim, uint32_t* no
     if (e->sharded()) return fail(e, GSX_ESTATE, "connections are trimmed on unsharded engines only");
     if (e->n_nodes == 0) return GSX_OK;
     if (int rc = flush(e)) return rc;
-    const bool h_trim = !on_device(trim), h_nt = !node_trimmed || !on_device(node_trimmed);
     if (!G.key)
         if (int rc = dalloc(e, &G.key, e->E)) return rc;
-    if (h_trim && !G.trim_buf)
-        if (int rc = dalloc(e, &G.trim_buf, e->E)) return rc;
-    if (h_nt && !G.nt_buf)
-        if (int rc = dalloc(e, &G.nt_buf, e->n_nodes)) return rc;
-    uint8_t* const d_trim = h_trim ? G.trim_buf : trim;
-    uint32_t* const d_nt = h_nt ? G.nt_buf : node_trimmed;
+    OutBinder B(e);
+    uint8_t* const d_trim = B.bind(trim, G.trim_buf, e->E, false);
+    uint32_t* d_nt = B.bind(node_trimmed, G.nt_buf, e->n_nodes, false);
+    if (!d_nt) d_nt = B.scratch(G.nt_buf, e->n_nodes, false);  // (the kernel always counts the rows' trims)
+    if (B.rc) return B.rc;
     const gsx::TagState t = dev_tags(e);
-    TagRegion reg(e);
+    LaunchRegion reg(e);
     HIPCHK(e, reg.begin());
     HIPCHK(e, gsx::launch_conn_values(t, nullptr, nullptr, G.key, e->stream));
     HIPCHK(e, gsx::launch_conn_trim(t, e->d_row_ptr, G.key, low_water, G.long_rows, G.n_long, d_trim, d_nt, e->stream));
     HIPCHK(e, reg.end());
-    if (h_trim && e->E) HIPCHK(e, hipMemcpyAsync(trim, d_trim, e->E, hipMemcpyDeviceToHost, e->stream));
-    if (node_trimmed && h_nt)
-        HIPCHK(e, hipMemcpyAsync(node_trimmed, d_nt, 4 * (size_t)e->n_nodes, hipMemcpyDeviceToHost, e->stream));
-    if (h_trim || (node_trimmed && h_nt)) HIPCHK(e, hipStreamSynchronize(e->stream));
-    return GSX_OK;
+    return B.finish();
 }
 
 int gsx_prop_duplicates(gsx_engine* e, uint64_t* rows, size_t n_words) {
